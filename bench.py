@@ -26,9 +26,21 @@ alternate over two streams, each stream with its own launch group of
 distinct batches (C2: 2,048 distinct batches, ~20 GB of patterns and
 outputs), so that no pass finds the previous pass's index lines in cache.
 Inputs (text, blob, index, patterns)
-are resident in HBM before the timed region.  The K steps are timed as a
-whole and repeated until the timed region lasts at least --min-seconds
-(0.2 s): a few-hundred-microsecond region is noise.
+are resident in HBM before the timed region.  `--steps K` times exactly K
+steps, once: K // group whole launches and one launch of the next group's
+first K % group batches (`--warmup W`: W steps of warm-up, in whole launches,
+every launch group at least once).  Without --steps, 800 steps rounded up to
+whole launches are timed as a whole and repeated until the timed region lasts
+at least --min-seconds: a few-hundred-microsecond region is noise.
+`ms_per_step` is the timed region over the steps it ran.
+
+A plain run sets up, warms up, times the steps and prints the result line.
+`--dump-outputs DIR` also writes what the last timed step computed as
+DIR/<name>.npy (dump_outputs below); the inputs are seeded, so two builds run
+with the same arguments can be compared array for array.  Everything else
+below — the blob_layout, single_batch and derived legs, k_search alone, the
+PCIe upload, the self-location check, the CPU baseline and the bit-exact
+checks against it — runs only with `--full`.
 
 Multi-GPU: one process per GPU.  Under torchrun (WORLD_SIZE set) this process
 is one rank; `--gpus N` without torchrun starts the N ranks itself (a
@@ -118,8 +130,20 @@ def parse():
                     help="ranks, one GPU each (default: WORLD_SIZE under torchrun, else 1); without torchrun, "
                          "N > 1 starts the N ranks itself")
     ap.add_argument("--steps", type=int, default=0,
-                    help="batches per timed pass (default: 800, or the whole sharded job for c3/c5)")
-    ap.add_argument("--warmup", type=int, default=10)
+                    help="batches (steps) timed, exactly: whole launches and one partial launch, one pass "
+                         "(default: 800 rounded up to whole launches, passes repeated for --min-seconds; "
+                         "c3/c5: the whole sharded job)")
+    ap.add_argument("--warmup", type=int, default=10,
+                    help="warm-up steps (batches), rounded up to whole launches; every launch group runs at "
+                         "least once whatever this says")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure and check everything else: the PCIe upload, k_search "
+                         "alone (roofline.kernel), the self-location check, the single_batch and blob_layout "
+                         "legs, the CPU baseline with its bit-exact check, and what --verify-job, --derived and "
+                         "--single-batch-only ask for")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (its batch's counts, offsets and locations, and "
+                         "the location totals of every batch of the last launch) as DIR/<name>.npy (float64)")
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
     ap.add_argument("--text-len", type=int, default=0, help="override the config's text length")
     ap.add_argument("--patterns", type=int, default=0, help="patterns per batch (target, for sharded jobs)")
@@ -180,7 +204,11 @@ def parse():
                          "suffix (upper bound of the cache reuse a suffix sort would buy; not a valid headline)")
     ap.add_argument("--presort-symbols", type=int, default=14,
                     help="--presorted: the sort key is the last this many symbols (order within a key kept)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    for flag in ("verify_job", "derived", "single_batch_only"):
+        if getattr(args, flag) and not args.full:
+            ap.error(f"--{flag.replace('_', '-')} asks for a leg that runs only with --full")
+    return args
 
 
 def log(*a):
@@ -292,21 +320,35 @@ class Workload:
         self.n_groups = -(-len(self.batches) // GR)
         self.bind()
         self.cursor = 0
+        self.last = None  # the launch group (or partial group) the timed region launched last
         # the batches were made on torch's stream; the launches use self.streams
         torch.cuda.synchronize()
 
     def bind(self):
         """(Re)build each launch group's job queue from the batches' current buffers."""
+        self.groups = [self.group_of(g, self.batches[g * self.GR:(g + 1) * self.GR]) for g in range(self.n_groups)]
+        self.partials = {}
+
+    def group_of(self, g, sel):
         ix = self.ix
-        self.groups = []
-        for g in range(self.n_groups):
-            sel = self.batches[g * self.GR:(g + 1) * self.GR]
-            q = ix.job_queue([ix.locate_job(b["pat"].data_ptr(), b["off"].data_ptr(), b["n"], b["loff"].data_ptr(),
-                                            b["locs"].data_ptr(), b["cap"], b["need"].data_ptr(),
-                                            b["ws_t"].data_ptr(), b["ws_t"].numel(), d_counts=b["cnt"].data_ptr(),
-                                            stage_kb=self.stage_kb, fixed_len=self.fixed) for b in sel])
-            self.groups.append(dict(queue=q, stream=self.streams[g % len(self.streams)], batches=sel,
-                                    patterns=sum(b["n"] for b in sel)))
+        q = ix.job_queue([ix.locate_job(b["pat"].data_ptr(), b["off"].data_ptr(), b["n"], b["loff"].data_ptr(),
+                                        b["locs"].data_ptr(), b["cap"], b["need"].data_ptr(),
+                                        b["ws_t"].data_ptr(), b["ws_t"].numel(), d_counts=b["cnt"].data_ptr(),
+                                        stage_kb=self.stage_kb, fixed_len=self.fixed) for b in sel])
+        return dict(queue=q, stream=self.streams[g % len(self.streams)], batches=sel,
+                    patterns=sum(b["n"] for b in sel))
+
+    def partial(self, g, r):
+        """Launch group g cut to its first r batches (the last launch of a pass
+        of a step count that is no multiple of GR), on g's stream."""
+        if (g, r) not in self.partials:
+            self.partials[g, r] = self.group_of(g, self.groups[g]["batches"][:r])
+        return self.partials[g, r]
+
+    def launch_partial(self, g, r):
+        grp = self.partial(g, r)
+        self.ix.locate_group_async(grp["queue"], stream=grp["stream"].cuda_stream)
+        return grp
 
     def rebind(self, outputs):
         """outputs[k] = (counts view, locations view) for batch k."""
@@ -349,25 +391,33 @@ class Workload:
 
 
 def timed_passes(torch, dist, dist_on, w, launches, warmup, min_seconds, event_every, on_launch=None,
-                 pre_launch=None, drain=None):
+                 pre_launch=None, drain=None, tail=0, exact=False):
     """Warm up (`warmup` launches, every launch group at least once), then time
-    passes of `launches` launches (groups cycled) until the region lasts
-    min_seconds.  Returns (elapsed_s, passes, batches_per_pass,
-    patterns_per_pass, timing)."""
+    passes of `launches` launches (groups cycled), each pass ending with a
+    launch of the next group's first `tail` batches when tail > 0.  The passes
+    are repeated until the region lasts min_seconds; `exact`: one pass, so that
+    exactly launches * GR + tail batches are timed.  Returns (elapsed_s, passes,
+    batches_per_pass, patterns_per_pass, timing)."""
     ix = w.ix
     for q in range(max(warmup, w.n_groups)):
         w.launch(q % w.n_groups)
+    if tail:
+        w.launch_partial(launches % w.n_groups, tail)
     torch.cuda.synchronize()
     w.check_capacity()
     w.cursor = 0
     count = [0, 0]
 
     def one_pass():
-        for _ in range(launches):
+        for q in range(launches + (1 if tail else 0)):
             g = w.cursor % w.n_groups
             if pre_launch:
                 pre_launch(g, w.groups[g])
-            gi, grp = w.launch_next()
+            if q < launches:
+                gi, grp = w.launch_next()
+            else:
+                gi, grp = g, w.launch_partial(g, tail)
+            w.last = grp
             count[0] += len(grp["batches"])
             count[1] += grp["patterns"]
             if on_launch:
@@ -375,19 +425,21 @@ def timed_passes(torch, dist, dist_on, w, launches, warmup, min_seconds, event_e
         if drain:
             drain()
 
-    # calibrate the pass count (untimed), the same on every rank
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    one_pass()
-    torch.cuda.synchronize()
-    t1 = time.perf_counter() - t0
-    # (the calibration pass runs colder than the timed ones: a 30 % margin keeps
-    # the timed region at or above min_seconds)
-    passes = max(1, math.ceil(1.3 * min_seconds / max(t1, 1e-6)))
-    if dist_on:
-        pt = torch.tensor([passes], dtype=torch.int64, device="cuda")
-        dist.all_reduce(pt, op=dist.ReduceOp.MAX)
-        passes = int(pt.item())
+    passes = 1
+    if not exact:
+        # calibrate the pass count (untimed), the same on every rank
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        one_pass()
+        torch.cuda.synchronize()
+        t1 = time.perf_counter() - t0
+        # (the calibration pass runs colder than the timed ones: a 30 % margin keeps
+        # the timed region at or above min_seconds)
+        passes = max(1, math.ceil(1.3 * min_seconds / max(t1, 1e-6)))
+        if dist_on:
+            pt = torch.tensor([passes], dtype=torch.int64, device="cuda")
+            dist.all_reduce(pt, op=dist.ReduceOp.MAX)
+            passes = int(pt.item())
     ix.timing_read()
     ix.timing_enable(True, every=event_every)
     if dist_on:
@@ -405,8 +457,9 @@ def timed_passes(torch, dist, dist_on, w, launches, warmup, min_seconds, event_e
     return elapsed, passes, count[0] // passes, count[1] // passes, ix.timing_read()
 
 
-def capture_pass(torch, w, launches):
-    """One pass — `launches` launches, group q on its own stream q % S — captured
+def capture_pass(torch, w, launches, tail=0):
+    """One pass — `launches` launches, group q on its own stream q % S, then the
+    next group's first `tail` batches when tail > 0 — captured
     in a HIP graph: the other streams fork from the first and join it at the
     end, so the replay keeps the launches' concurrency.  The engine's launch
     path is capture-safe (no synchronous call; timing must be off)."""
@@ -420,7 +473,9 @@ def capture_pass(torch, w, launches):
             st.wait_event(fork)
         w.cursor = 0
         for _ in range(launches):
-            w.launch_next()
+            w.last = w.launch_next()[1]
+        if tail:
+            w.last = w.launch_partial(w.cursor % w.n_groups, tail)
         for st in w.streams[1:]:
             join = torch.cuda.Event()
             join.record(st)
@@ -429,21 +484,25 @@ def capture_pass(torch, w, launches):
     return g
 
 
-def timed_graph(torch, dist, dist_on, w, launches, warmup, min_seconds):
+def timed_graph(torch, dist, dist_on, w, launches, warmup, min_seconds, tail=0, exact=False):
     """timed_passes with every pass a replay of one captured graph."""
     for q in range(max(warmup, w.n_groups)):
         w.launch(q % w.n_groups)
+    if tail:
+        w.launch_partial(launches % w.n_groups, tail)
     torch.cuda.synchronize()
     w.check_capacity()
     w.ix.timing_enable(False)
-    g = capture_pass(torch, w, launches)
-    per = sum(w.groups[q % w.n_groups]["patterns"] for q in range(launches))
-    nbat = sum(len(w.groups[q % w.n_groups]["batches"]) for q in range(launches))
+    g = capture_pass(torch, w, launches, tail)
+    ran = [w.groups[q % w.n_groups] for q in range(launches)] + \
+        ([w.partial(launches % w.n_groups, tail)] if tail else [])
+    per = sum(grp["patterns"] for grp in ran)
+    nbat = sum(len(grp["batches"]) for grp in ran)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     g.replay()
     torch.cuda.synchronize()
-    passes = max(1, math.ceil(1.3 * min_seconds / max(time.perf_counter() - t0, 1e-6)))
+    passes = 1 if exact else max(1, math.ceil(1.3 * min_seconds / max(time.perf_counter() - t0, 1e-6)))
     if dist_on:
         pt = torch.tensor([passes], dtype=torch.int64, device="cuda")
         dist.all_reduce(pt, op=dist.ReduceOp.MAX)
@@ -493,6 +552,29 @@ def self_location(w, P):
         hit[owner[bl.astype(np.int64) == st[owner]]] = True
         ok = ok and bool(hit.all() and (cnt >= 1).all())
     return ok
+
+
+def dump_outputs(path, w, P):
+    """What a caller of the timed path holds after its last step, as
+    path/<name>.npy (float64: exact for every count, offset and position below
+    2^53): the last batch of the last launch — `counts` (occurrences per
+    pattern), `offsets` (n + 1 offsets into the locations) and `locations`
+    (offsets[-1] text positions) — and `location_totals`, the number of
+    locations of every batch of that launch.  ~2.5 MB at C2."""
+    w.sync()
+    os.makedirs(path, exist_ok=True)
+    pdt_np = np.uint32 if P == 4 else np.uint64
+    sel = w.last["batches"]
+    bt = sel[-1]
+    offs = bt["loff"].cpu().numpy().view(np.uint64)
+    arrays = {
+        "counts": bt["cnt"][:bt["n"]].cpu().numpy().view(pdt_np),
+        "offsets": offs,
+        "locations": bt["locs"][:int(offs[-1])].cpu().numpy().view(pdt_np),
+        "location_totals": w.torch.cat([b["need"] for b in sel]).cpu().numpy(),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def traffic_of(path, key):
@@ -613,7 +695,7 @@ def main():
 
     # PCIe: what loading this blob from host memory costs (pinned -> HBM)
     upload_s = None
-    if rank == 0 and blob_len <= (16 << 30):
+    if args.full and rank == 0 and blob_len <= (16 << 30):
         h_blob = torch.empty(blob_len, dtype=torch.uint8, pin_memory=True)
         h_blob.copy_(d_blob)
         d_tmp = torch.empty_like(d_blob)
@@ -647,6 +729,7 @@ def main():
 
     NB = -(-max(S * GR, args.batches) // (S * GR)) * (S * GR)  # weak: whole groups on every stream
     plan = job_starts = None
+    tail, exact = 0, False
     if strong:
         # the global job (the same on every rank), dealt out by JobPlan
         # with gathers (N > 1): one launch group per stream (each of GR / S batches), so that a group's
@@ -668,8 +751,14 @@ def main():
         w = Workload(torch, ix, d_text, m, weak_starts(NB), P, S, GR, fixed, dev)
         if args.presorted or args.xcd_partitioned:
             arrange(torch, w, B, m, GR, dev, args.presorted, args.presort_symbols, cfg["alphabet"])
-        steps = args.steps or 800
-        launches = -(-steps // GR)
+        if args.steps > 0:
+            # exactly --steps batches, once: whole launches and the next group cut to the remainder
+            steps, exact = args.steps, True
+            launches, tail = divmod(steps, GR)
+        else:
+            steps = 800
+            launches = -(-steps // GR)
+    warm = -(-max(args.warmup, 0) // GR)  # --warmup counts steps; the warm-up runs whole launches
     torch.cuda.synchronize()
 
     jg = None
@@ -679,7 +768,7 @@ def main():
         # kernels' outputs straight into the gather slabs: a sharded job's
         # (c3/c5), or every rank's own batches (c2 weak scaling), so that the
         # results are concatenated on every rank inside the timed step
-        for q in range(max(args.warmup, w.n_groups)):
+        for q in range(max(warm, w.n_groups)):
             w.launch(q % w.n_groups)
         torch.cuda.synchronize()
         needs = w.check_capacity()
@@ -690,11 +779,12 @@ def main():
 
     # ---- timed region: compute ----------------------------------------------
     if args.graph:
-        elapsed, passes, per_pass, pats_pass, timing = timed_graph(torch, dist, dist_on, w, launches, args.warmup,
-                                                                   args.min_seconds)
+        elapsed, passes, per_pass, pats_pass, timing = timed_graph(torch, dist, dist_on, w, launches, warm,
+                                                                   args.min_seconds, tail=tail, exact=exact)
     else:
-        elapsed, passes, per_pass, pats_pass, timing = timed_passes(torch, dist, dist_on, w, launches, args.warmup,
-                                                                    args.min_seconds, args.event_every)
+        elapsed, passes, per_pass, pats_pass, timing = timed_passes(torch, dist, dist_on, w, launches, warm,
+                                                                    args.min_seconds, args.event_every, tail=tail,
+                                                                    exact=exact)
     if dist_on:
         elapsed = D.max_over_ranks(elapsed, device=dev)
     # every pattern a launch ran counts (a pass of K steps runs ceil(K / GR) whole launches)
@@ -745,7 +835,7 @@ def main():
 
         e2, p2, _, pats2, _ = timed_passes(torch, dist, dist_on, w, launches, 0, args.min_seconds,
                                            args.event_every, on_launch=on_launch, pre_launch=pre_launch,
-                                           drain=drain)
+                                           drain=drain, tail=tail, exact=exact)
         e2 = D.max_over_ranks(e2, device=dev)
         pt2 = torch.tensor([pats2 * p2], dtype=torch.int64, device=dev)
         dist.all_reduce(pt2)
@@ -769,6 +859,13 @@ def main():
                        "gathered_over_result": jg.bytes_per_pass() / max(jg.result_bytes(), 1)})
         if args.gather == "counts":
             jg.gather_all()  # the locations once, after the timed region (assemble below)
+            torch.cuda.synchronize()
+        else:
+            # a launch group that no timed launch reached (--steps below one cycle of the groups): its
+            # warm-up results gathered once, untimed, so that the assembled job below is whole
+            for gi in range(w.n_groups):
+                if gi not in gathered:
+                    jg.gather(gi)
             torch.cuda.synchronize()
     if jg is not None:
         # the job's flat (offsets, locations) on the device; this rank's part
@@ -803,8 +900,13 @@ def main():
     alg_per_pattern = per_pattern + per_occ * my_occ / max(my_pats, 1)
     per_gpu = value_compute / max(world, 1)
     achieved = alg_per_pattern * per_gpu / 1e9
+    # what the last timed step computed, before any later leg runs the batches again
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, w, P)
+
     fused0 = ix.info().get("launches_fused", 0)
-    kt = kernel_pass(torch, w, max(1, args.kernel_launches))
+    # (k_search alone takes launches of its own: --full)
+    kt = kernel_pass(torch, w, max(1, args.kernel_launches)) if args.full else {}
     # launches in launch order of small batches run as one kernel (k_locate): its "search phase" is the whole launch
     fused = ix.info().get("launches_fused", 0) > fused0
     ks, ke, kl = (kt.get(x, {}) for x in ("locate.search", "locate.emit", "locate"))
@@ -827,7 +929,7 @@ def main():
         "achieved_basis": "per-step cost: the reference algorithm's bytes per pattern (SURVEY.md 8(d), "
                           "alg_bytes_per_pattern) x the timed region's patterns/s per GPU",
         "alg_bytes_per_pattern": alg_per_pattern,
-        "kernel": {
+        "kernel": None if not args.full else {
             "name": ("search phase of a grouped launch: k_group_key + k_group_scan + k_group_place + "
                      "k_search_grouped + k_group_tiles" if grouped else
                      "k_locate (fused: search, tile-count hand-off, offsets and locations in one kernel)" if fused
@@ -860,7 +962,7 @@ def main():
             "fabric_read_bytes_per_pattern": tr["fabric_bytes_per_launch"] / tppl,
             "traffic_frac_effective": tpp * per_gpu / 1e9 / HBM_PEAK_GBS,
         })
-        if tr.get("search_kernel"):
+        if tr.get("search_kernel") and roof["kernel"] is not None:
             roof["kernel"]["traffic_bytes_per_pattern"] = tr["search_kernel"].get("traffic_bytes_per_pattern")
             roof["kernel"]["fabric_requests_per_pattern"] = tr["search_kernel"].get("fabric_requests_per_pattern")
         if req:
@@ -886,9 +988,11 @@ def main():
         "timed_passes": passes_timed,
         "batches_per_pass": per_pass,
         "timed_region_s": region_s,
-        "steps_what": "batches (steps) timed: whole launches of up to batches_per_launch batches, passes repeated "
-                      "until the region lasts >= --min-seconds; the requested --steps is rounded up to whole "
-                      "launches per pass" + ("; N > 1: the passes with the in-step all-gathers" if dist_on else ""),
+        "steps_what": ("batches (steps) timed: exactly --steps, in one pass of whole launches of batches_per_launch "
+                       "batches and one launch of the remainder" if exact else
+                       "batches (steps) timed: whole launches of up to batches_per_launch batches, passes repeated "
+                       "until the region lasts >= --min-seconds") +
+                      ("; N > 1: the passes with the in-step all-gathers" if dist_on else ""),
         "higher_is_better": True,
         "scaling": "strong" if strong else "weak",
         "vs_baseline": None,
@@ -913,7 +1017,8 @@ def main():
         "roofline": roof,
         "kernels_ms_per_launch_timed_region": per_launch_ms(timing),
         "occurrences_batch0": total_occ,
-        "self_location_check": self_location(w, P),
+        "self_location_check": self_location(w, P) if args.full else None,
+        "full": bool(args.full),
         "build_s": build_s,
         "load_s": load_s,
         "upload_s": upload_s,
@@ -954,7 +1059,7 @@ def main():
         del orc
 
     # ---- one batch per call (the config's own batch, N = 1) ------------------
-    if rank == 0 and world == 1 and not strong and not args.no_single_batch:
+    if args.full and rank == 0 and world == 1 and not strong and not args.no_single_batch:
         result["single_batch"] = single_batch_leg(torch, ix, load, d_text, n, m, B, fixed, dev, args.seed,
                                                   min(args.min_seconds, 1.0), pdt_t, P, GR, S)
     if args.single_batch_only:
@@ -966,21 +1071,21 @@ def main():
     # the workload's distinct batches — at C2's 2,048: every 66th, so every
     # kernel-argument group of 256 of both grouped launches is sampled; host copies)
     host_batches, host_idx, n_distinct = [], [], len(w.batches)
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         host_idx = sorted({int(round(x)) for x in np.linspace(0, n_distinct - 1, min(32, n_distinct))})
         for bi in host_idx:
             bt = w.batches[bi]
             bo = bt["loff"].cpu().numpy().view(np.uint64).copy()
             host_batches.append((bt["pat"].cpu().numpy(), bt["n"], bo,
                                  bt["locs"][:int(bo[-1])].cpu().numpy().view(pdt_np).copy()))
-    if world == 1 and not args.no_blob_layout and args.options != BLOB_LAYOUT:
+    if args.full and world == 1 and not args.no_blob_layout and args.options != BLOB_LAYOUT:
         w.release()
         w = None
         ixb, load_b = load(BLOB_LAYOUT)
         infob = ixb.info()
         wb = Workload(torch, ixb, d_text, m, weak_starts(NB), P, S, GR, fixed, dev)
         bsteps = args.steps or 800
-        eb, pb, _, patsb, tb = timed_passes(torch, dist, dist_on, wb, -(-bsteps // GR), args.warmup,
+        eb, pb, _, patsb, tb = timed_passes(torch, dist, dist_on, wb, -(-bsteps // GR), warm,
                                             args.min_seconds, args.event_every)
         ktb = kernel_pass(torch, wb, max(1, args.kernel_launches)).get("locate.search", {})
         result["blob_layout"] = {
@@ -1005,7 +1110,7 @@ def main():
         infod = ixd.info()
         wd = Workload(torch, ixd, d_text, m, weak_starts(NB), P, S, GR, fixed, dev)
         dsteps = args.steps or 800
-        ed, pd, _, patsd, td_t = timed_passes(torch, dist, dist_on, wd, -(-dsteps // GR), args.warmup,
+        ed, pd, _, patsd, td_t = timed_passes(torch, dist, dist_on, wd, -(-dsteps // GR), warm,
                                               args.min_seconds, args.event_every)
         vd = patsd * pd / ed
         dt = 1.0 / value_compute - 1.0 / vd  # seconds saved per pattern
@@ -1025,7 +1130,7 @@ def main():
     # ---- CPU baseline + bit-exact check (rank 0, N=1 only) -------------------
     # The oracle answers the GPU's batches in turn (whole batches, cycled) for
     # >= cpu_seconds per leg; every batch it answers is compared with the GPU.
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         from oracle import oracle as O
         orc = oracle_index(O, d_blob, blob_len, P, cfg)
         cores, src = usable_cores()

@@ -47,8 +47,8 @@ def test_c3_full_job_one_gpu():
     results are written into the exactly sized gather slabs, the job's flat
     (offsets, locations) is assembled on the device, and rank 0 compares all
     10 M counts and every location with the CPU oracle."""
-    p = run_bench(["--config", "c3", "--verify-job", "--no-cpu", "--no-blob-layout", "--min-seconds", "0.05",
-                   "--warmup", "0"])
+    p = run_bench(["--config", "c3", "--full", "--verify-job", "--no-cpu", "--no-blob-layout", "--min-seconds",
+                   "0.05", "--warmup", "0"])
     assert p.returncode == 0, p.stderr[-3000:]
     r = last_json(p.stdout)
     assert r["scaling"] == "strong" and r["config"]["global_batch"] == 10_000_000
@@ -70,8 +70,8 @@ def test_rccl_world1_strong_job():
     gathered slabs (assemble) and all 800,000 patterns checked against the
     oracle (--verify-job).  So the driver's 8-GPU run is not this code's first
     contact with RCCL."""
-    p = run_bench(["--config", "c3", "--text-len", "50000000", "--total-patterns", "800000", "--verify-job",
-                   "--no-cpu", "--min-seconds", "0.05", "--warmup", "0"],
+    p = run_bench(["--config", "c3", "--text-len", "50000000", "--total-patterns", "800000", "--full",
+                   "--verify-job", "--no-cpu", "--min-seconds", "0.05", "--warmup", "0"],
                   env_extra={"FMX_BENCH_DIST": "1"}, torchrun=1)
     assert p.returncode == 0, p.stderr[-3000:]
     r = last_json(p.stdout)
@@ -123,7 +123,7 @@ def test_gloo_two_ranks_one_gpu_strong():
     world).  A sharded job with the in-step gathers (one collective per launch
     group); the assembled job equals the oracle's answer."""
     p = run_bench(["--gpus", "2", "--config", "c3", "--text-len", "50000000", "--total-patterns", "800000",
-                   "--verify-job", "--no-cpu", "--min-seconds", "0.05", "--warmup", "0"],
+                   "--full", "--verify-job", "--no-cpu", "--min-seconds", "0.05", "--warmup", "0"],
                   env_extra={"FMX_BENCH_BACKEND": "gloo"})
     assert p.returncode == 0, p.stderr[-3000:]
     r = last_json(p.stdout)
@@ -144,8 +144,9 @@ def test_gloo_two_ranks_weak_gather():
     group's results are all-gathered inside the timed step (one collective
     per launch, exactly sized slabs), the job assembled on the device holds
     this rank's part intact, and the padding stays under 1.25x."""
+    # (656 steps: ten whole launches of 64 and one of the remaining 16, so that the timed region is no blink)
     p = run_bench(["--gpus", "2", "--config", "c2", "--text-len", "20000000", "--patterns", "20000", "--group", "64",
-                   "--steps", "16", "--batches", "16", "--no-cpu", "--min-seconds", "0.05", "--warmup", "0"],
+                   "--steps", "656", "--batches", "16", "--no-cpu", "--min-seconds", "0.05", "--warmup", "0"],
                   env_extra={"FMX_BENCH_BACKEND": "gloo"})
     assert p.returncode == 0, p.stderr[-3000:]
     r = last_json(p.stdout)
