@@ -240,8 +240,7 @@ fmx_status fmx_count_batch_async(fmx_index *ix, const uint8_t *d_bytes, const ui
  * The workspace must be 16-byte aligned (FMX_E_ARG otherwise: the grouped
  * passes read and write it as 16-B vectors; hipMalloc gives 256-B alignment).
  * A workspace needs no initialisation (a grouped launch zeroes its key
- * counters on its stream first; only the FMX_SEARCH_PERSISTENT=1 A/B variant
- * wants its first 4 bytes zero) and belongs to this index: its launches are
+ * counters on its stream first) and belongs to this index: its launches are
  * ordered on one stream at a time.  A locate is k_search + k_emit.  A
  * grouped locate first deals the launch's patterns out in the order of their
  * last symbols, so that patterns whose backward searches share their first

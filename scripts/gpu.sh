@@ -16,7 +16,7 @@
 #   presort  bench.py --presorted (L = 8, 12) and the same command without (upper bound of a longer key)
 #   refineab k_group_refine on / off, alternating twice
 #   c1ab     C1 at a 2 s and a 0.2 s timed region
-#   knobs    headline A/B: no XCD order, 3 streams, 128 x 4 streams, two patterns per lane
+#   knobs    headline A/B: no XCD order, 3 streams, 128 x 4 streams
 #   freshreps  test_every_layout_grouped[4-2-*] in 12 fresh processes, then the grouped file 3 times (FMX_DEBUG=1)
 #   countab  the count pass decoding the key's bytes only (this build) vs the whole pattern
 #            (build_ab/libfmx_fullcount.so via FMX_LIB), alternating twice
@@ -42,8 +42,6 @@
 #   c4ab     C4 at 1,024 per launch: grouped (default) vs launch order, alternating twice
 #   streamab C2 on 2 vs 3 streams at 1,024 batches per launch, alternating twice
 #   foldab   C2: k_emit's own tile sums vs k_scan first (FMX_EMIT_FOLD=0), and the refine pass, alternating twice
-#   slotab   C2 with the per-XCD sub-runs (8 slots) vs one run per key (sview-fmindex_amd/lib/ab/libfmx_s1.so),
-#            alternating twice, then a one-stream kernel trace of each
 #   megab    C2 at 256 / 512 / 1,024 batches per launch (one grouped launch over 2-4 kernel-argument groups), twice
 #   megatest test_gpu_mega.py (1,024-batch grouped launch, two-stream fused launches), test_gpu_fused.py,
 #            test_gpu_provenance.py
@@ -58,7 +56,6 @@
 #   m2048ab  C2 at 2,048 batches per launch (the FMX_MAX_MEGA=2048 build) vs 1,024, alternating twice
 #   tcc      the TCC hit/miss PMC pass alone (C2, shipped launch shape)
 #   c4walk   C4 with vs without the walk line in its multi-line records, alternating twice
-#   c4pair   C4 one vs two patterns per lane in the grouped search, alternating twice; C2 two per lane once
 #   shapes   the per-rank shapes of C3 (10 M / N) and C5 (1 M / N) at N = 1, 2, 4, 8 on one GPU
 #   gloo2g   bench.py --gpus 2 over gloo on the one GPU with --gather all and --gather counts
 #   ticketab the fused launch's tickets vs workgroup index order: single batch and C1, alternating twice
@@ -119,7 +116,6 @@ for step in "$@"; do
             FMX_GROUPED_XCD=0 run knob_noxcd 300 $B || exit 1
             run knob_s3 300 $B --streams 3 || exit 1
             run knob_g128_s4 300 $B --group 128 --streams 4 || exit 1
-            FMX_GROUPED_PAIR=1 run knob_pair 300 $B || exit 1
             run knob_ref2 300 $B || exit 1 ;;
         freshreps)
             for i in 1 2 3 4 5 6 7 8 9 10 11 12; do
@@ -222,19 +218,6 @@ for step in "$@"; do
             done ;;
         groupedtest) run pytest_grouped 900 python -u -m pytest tests/test_gpu_grouped.py tests/test_gpu_fused.py -x -v \
                 --timeout 300 --timeout-method thread || exit 1 ;;
-        slotab)
-            B="python -u bench.py --full --no-cpu --no-blob-layout --no-single-batch"
-            for r in 1 2; do
-                run "slots8_$r" 400 $B || exit 1
-                FMX_LIB=$PWD/sview-fmindex_amd/lib/ab/libfmx_s1.so run "slots1_$r" 400 $B || exit 1
-            done
-            run slots8_trace 400 rocprofv3 --kernel-trace --stats -d "$OUT/s8" -o run --output-format csv -- \
-                python3 -u bench.py --full --streams 1 --no-cpu --no-blob-layout --no-single-batch || exit 1
-            shrink "$OUT/s8"
-            FMX_LIB=$PWD/sview-fmindex_amd/lib/ab/libfmx_s1.so run slots1_trace 400 rocprofv3 --kernel-trace --stats \
-                -d "$OUT/s1" -o run --output-format csv -- \
-                python3 -u bench.py --full --streams 1 --no-cpu --no-blob-layout --no-single-batch || exit 1
-            shrink "$OUT/s1" ;;
         c4mega)  # C4 at 1,024 batches per launch: launch order vs grouped (keyed on 3 residues; + refine)
             B="python -u bench.py --full --config c4 --no-cpu --no-blob-layout --no-single-batch"
             FMX_GROUPED=0 run c4_lo_g256 400 $B --group 256 || exit 1
@@ -334,20 +317,6 @@ for step in "$@"; do
                 run "c4_walk_$i" 400 python -u bench.py --full $B || exit 1
                 FMX_OCC_WALK=0 run "c4_nowalk_$i" 400 python -u bench.py --full $B || exit 1
             done ;;
-        contigab)  # records in physically contiguous memory (FMX_OCC_CONTIG=1) vs hipMalloc's, same box, alternating;
-            # then the translation pass on C4 with them
-            B="--no-cpu --no-blob-layout --no-single-batch"
-            for i in 1 2; do
-                for c in c4 c2; do
-                    run "${c}_heap_$i" 400 python -u bench.py --full --config $c $B || exit 1
-                    FMX_OCC_CONTIG=1 run "${c}_contig_$i" 400 python -u bench.py --full --config $c $B || exit 1
-                done
-            done
-            P="--config c4 --streams 1 --no-cpu --no-blob-layout --no-single-batch --min-seconds 0.5"
-            FMX_OCC_CONTIG=1 run pmc_tlb_c4_contig 120 rocprofv3 --pmc TCP_UTCL1_TRANSLATION_HIT_sum \
-                TCP_UTCL1_TRANSLATION_MISS_sum --kernel-trace -d "$OUT/pmc_tlb_c4_contig" -o run --output-format csv \
-                -- python3 -u bench.py --full $P || exit 1
-            shrink "$OUT/pmc_tlb_c4_contig" ;;
         configs)
             for c in c1 c3 c4 c5; do
                 run "bench_$c" 600 python -u bench.py --full --config $c || exit 1
@@ -372,15 +341,6 @@ for step in "$@"; do
                 run "c1_tk_$r" 300 python -u bench.py --full --config c1 --no-cpu || exit 1
                 FMX_FUSED_TICKETS=0 run "c1_idx_$r" 300 python -u bench.py --full --config c1 --no-cpu || exit 1
             done ;;
-        c4pair)  # C4 (grouped, 1,024 per launch): one vs two patterns per lane in the grouped search
-            # (FMX_GROUPED_PAIR=1), alternating twice; then C2 with two per lane once
-            B="python -u bench.py --full --config c4 --no-cpu --no-blob-layout --no-single-batch"
-            for r in 1 2; do
-                run "c4_k1_$r" 400 $B || exit 1
-                FMX_GROUPED_PAIR=1 run "c4_k2_$r" 400 $B || exit 1
-            done
-            FMX_GROUPED_PAIR=1 run c2_k2 400 python -u bench.py --full --no-cpu --no-blob-layout --no-single-batch || exit 1
-            run c2_k1 400 python -u bench.py --full --no-cpu --no-blob-layout --no-single-batch || exit 1 ;;
         shapes)  # the per-rank shapes JobPlan deals at N = 1/2/4/8, each run on this one GPU (no gathers):
             # C3 10 M / N and C5 1 M / N patterns; and C3's N = 8 slab in launch order
             B="--no-cpu --no-blob-layout --no-single-batch"

@@ -546,6 +546,68 @@ hipError_t Stage::d2h(void *h, const void *d, uint64_t n, hipStream_t s) {
     return e;
 }
 
+// The launch policy of an index (the fused*, emit_*, grouped_*, group_* fields
+// of fmx_index) from the environment, read once at load, after gkey_len is
+// known.  Every variable, its values, [default] and what it does:
+//   FMX_FUSED            0 | 1 [1]   launches in launch order run as one kernel (k_locate) when they
+//                                    qualify (fmx_query.hip, launch_split); 0: always k_search + k_emit
+//   FMX_FUSED_MAX_TILES  n [none]    ... only launches of at most n tiles
+//   FMX_FUSED_TIMEOUT_MS ms [4000]   bound on a fused launch's waits (>= 1; then FMX_E_DEVICE, never a hang)
+//   FMX_FUSED_TICKETS    0 | 1 [1]   fused workgroups take their tile by ticket; 0 (A/B): by their index
+//   FMX_EMIT_CHAIN       0 | 1 [0]   (A/B) grouped launches end with k_emit_chain instead of
+//                                    k_group_tiles + k_emit when every batch has at most kFoldTiles tiles
+//   FMX_EMIT_FOLD        0 | 1       k_emit sums the earlier tiles' counts itself (1) or k_scan runs first
+//                                    (0) everywhere; unset: 1 in launch order up to kFoldTiles tiles, else 0
+//   FMX_GROUPED          0 | 1       0: no launch is grouped; 1: every launch that can be, those needing
+//                                    id-only records included; unset: from grouped_min patterns (below)
+//   FMX_GROUPED_MIN      n           grouped from n patterns per launch (overrides FMX_GROUPED's)
+//   FMX_GROUPED_RAW      0 | 1 [0]   (A/B) id-only sorted records even for patterns that pack, and
+//                                    launches needing them grouped from grouped_min
+//   FMX_GROUPED_XCD      0 | 1 [1]   each XCD searches one eighth of the key order
+//   FMX_GROUPED_WSORT    0 | 1 [1]   the grouped search sorts each workgroup's patterns below the key
+//   FMX_GROUP_REFINE_MIN n [never]   grouped launches of at least n patterns run k_group_refine (on C2 at
+//                                    25.6 M per launch it costs 462 us and saves 352)
+//   FMX_GROUP_REFINE     0           never refine (beats FMX_GROUP_REFINE_MIN)
+//   FMX_GROUP_CHECK      0 | 1 [0]   (debug) grouped launches check their sorted order (kStatusCheck)
+static void read_policy_env(fmx_index *ix) {
+    const char *e;
+    if ((e = getenv("FMX_FUSED"))) ix->fused = e[0] != '0';
+    if ((e = getenv("FMX_FUSED_MAX_TILES"))) ix->fused_max_tiles = strtoull(e, nullptr, 0);
+    {
+        uint64_t ms = 4000;  // of the wall clock
+        if ((e = getenv("FMX_FUSED_TIMEOUT_MS"))) ms = std::max<uint64_t>(1, strtoull(e, nullptr, 0));
+        int khz = 0;
+        if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, ix->device) != hipSuccess || khz <= 0)
+            khz = 100000;
+        ix->fused_late_ticks = ms * (uint64_t)khz;
+    }
+    if ((e = getenv("FMX_FUSED_TICKETS"))) ix->fused_tickets = e[0] != '0';
+    if ((e = getenv("FMX_EMIT_CHAIN"))) ix->emit_chain = e[0] != '0';
+    if ((e = getenv("FMX_EMIT_FOLD"))) ix->emit_fold = e[0] != '0' ? 1 : 0;
+    // grouped by default: launches of at least 3 x 2^20 patterns whose key spans
+    // at least 5 symbols (DNA: 6; the crossover with launch order is ~2.5 M,
+    // profiles/r6/r6d_c3{g,o}_*), and of at least 2^26 whose key is shorter (a
+    // 20-residue alphabet keys on 3: grouping lost at 25.6 M patterns per
+    // launch and won at 102.4 M, profiles/r5/r5f_*, r5c4m_*).  DESIGN.md §5,
+    // "When grouping pays", and §6 hold the measurements.
+    ix->grouped_min = ix->gkey_len >= 5 ? (3ull << 20) : (1ull << 26);
+    // patterns too long to pack (id-only records) are grouped only on request:
+    // C5 (1 M x 150 bp) measured slower grouped (3.1 vs 3.5 x 10^8, DESIGN.md §5)
+    ix->grouped_raw_min = ~0ull;
+    if ((e = getenv("FMX_GROUPED"))) {
+        if (e[0] == '0') ix->grouped_min = ~0ull;
+        else if (e[0] == '1') ix->grouped_min = ix->grouped_raw_min = 1;
+    }
+    if ((e = getenv("FMX_GROUPED_MIN"))) ix->grouped_min = strtoull(e, nullptr, 10);
+    if ((e = getenv("FMX_GROUPED_RAW"))) ix->grouped_raw = e[0] == '1';
+    if (ix->grouped_raw) ix->grouped_raw_min = ix->grouped_min;
+    if ((e = getenv("FMX_GROUPED_XCD"))) ix->grouped_xcd = e[0] == '1';
+    if ((e = getenv("FMX_GROUPED_WSORT"))) ix->grouped_wsort = e[0] != '0';
+    if ((e = getenv("FMX_GROUP_REFINE_MIN"))) ix->group_refine_min = strtoull(e, nullptr, 10);
+    if ((e = getenv("FMX_GROUP_REFINE")) && e[0] == '0') ix->group_refine_min = ~0ull;
+    if ((e = getenv("FMX_GROUP_CHECK"))) ix->group_check = e[0] == '1';
+}
+
 static fmx_status finish_load(fmx_index *ix, uint32_t options) {
     QueryArgs &q = ix->qa;
     const BlobView &v = ix->bv;
@@ -580,23 +642,8 @@ static fmx_status finish_load(fmx_index *ix, uint32_t options) {
     }
     ix->slot_mu.reset(new (std::nothrow) std::mutex[kStatusSlots]);
     if (!ix->slot_mu) return FMX_E_DEVICE;
-    if (const char *e = getenv("FMX_FUSED_TICKETS")) ix->fused_tickets = e[0] != '0';
     if (hipStreamSynchronize(ix->stream) != hipSuccess) return FMX_E_DEVICE;
     ix->slots.assign(kStatusSlots, StatusSlot{});
-    if (const char *e = getenv("FMX_SEARCH_PERSISTENT")) ix->search_persistent = e[0] == '1';
-    // the fused launch (k_locate) and the bound on its waits: 4 s of the wall clock by default
-    if (const char *e = getenv("FMX_FUSED")) ix->fused = e[0] != '0';
-    if (const char *e = getenv("FMX_EMIT_CHAIN")) ix->emit_chain = e[0] != '0';
-    if (const char *e = getenv("FMX_EMIT_FOLD")) ix->emit_fold = e[0] != '0' ? 1 : 0;
-    if (const char *e = getenv("FMX_FUSED_MAX_TILES")) ix->fused_max_tiles = strtoull(e, nullptr, 0);
-    {
-        uint64_t ms = 4000;
-        if (const char *e = getenv("FMX_FUSED_TIMEOUT_MS")) ms = std::max<uint64_t>(1, strtoull(e, nullptr, 0));
-        int khz = 0;
-        if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, ix->device) != hipSuccess || khz <= 0)
-            khz = 100000;
-        ix->fused_late_ticks = ms * (uint64_t)khz;
-    }
     for (uint32_t i = kStatusSlots; i-- > 0;) ix->free_slots.push_back(i);
     {
         int idx = -1;
@@ -673,46 +720,7 @@ static fmx_status finish_load(fmx_index *ix, uint32_t options) {
     ix->gkey_len = 0;
     if (S >= 2)
         for (uint64_t bins = S; bins <= kGroupBins && ix->gkey_len < 16; bins *= S) ++ix->gkey_len;
-    // on by default for launches of at least 3 x 2^20 patterns whose key spans
-    // at least 5 symbols (DNA: 6), and of at least 2^26 whose key is shorter (a
-    // 20-residue alphabet keys on 3, no more than its k-mer seed: at 25.6 M
-    // patterns per launch grouping lost, 3.29 vs 3.59 x 10^9, profiles/r5/
-    // r5f_*; at 102.4 M it won, 3.68 vs 3.42-3.45, r5c4m_*).  Below ~1 M
-    // patterns the dealing out's fixed cost eats the sharing: at 256 batches
-    // of 1,000 (C1) launch order runs 8.0 vs 4.2 x 10^9 grouped (r5p_*,
-    // r5q_*), at 0.8 M patterns on 1 Gbp the two were equal and at 1.6 M
-    // grouping gained 6 % (round 3); at 25.6 M patterns it gains 4 % on a
-    // 4 Mbp text and 50 % from 16 Mbp up (r5q_size_*, r5r_size_*).  Round 6,
-    // C3's per-rank slabs on 1 Gbp (256 batches per launch, same box,
-    // profiles/r6/r6d_c3{g,o}_*): grouped vs launch order 2.97 vs 2.65 x 10^9
-    // at 5 M, 2.62 vs 2.61 at 2.5 M, 2.42 vs 2.54 at 1.6 M, 2.25 vs 2.48 at
-    // 1.25 M (C3's slab at 8 ranks) — the crossover is ~2.5 M, so 3 x 2^20.
-    ix->grouped_min = ix->gkey_len >= 5 ? (3ull << 20) : (1ull << 26);
-    if (const char *e = getenv("FMX_GROUPED")) {
-        if (e[0] == '0') ix->grouped_min = ~0ull;
-        else if (e[0] == '1') ix->grouped_min = 1;
-    }
-    if (const char *e = getenv("FMX_GROUPED_MIN")) ix->grouped_min = strtoull(e, nullptr, 10);
-    ix->grouped_xcd = 1;
-    if (const char *e = getenv("FMX_GROUPED_XCD")) ix->grouped_xcd = e[0] == '1';
-    ix->grouped_pair = 0;
-    if (const char *e = getenv("FMX_GROUPED_PAIR")) ix->grouped_pair = e[0] == '1';
-    ix->grouped_wsort = true;
-    if (const char *e = getenv("FMX_GROUPED_WSORT")) ix->grouped_wsort = e[0] != '0';
-    ix->grouped_raw = false;
-    if (const char *e = getenv("FMX_GROUPED_RAW")) ix->grouped_raw = e[0] == '1';
-    // patterns too long to pack (id-only records) are grouped only on request:
-    // C5 (1 M x 150 bp) measured slower grouped (3.1 vs 3.5 x 10^8, DESIGN.md §5)
-    ix->grouped_raw_min = ~0ull;
-    if (const char *e = getenv("FMX_GROUPED"))
-        if (e[0] == '1') ix->grouped_raw_min = 1;
-    if (ix->grouped_raw) ix->grouped_raw_min = ix->grouped_min;
-    // (opt-in: on C2 at 25.6 M patterns per launch the refine pass costs 462 us and
-    // saves 352 us of k_search_grouped)
-    ix->group_refine_min = ~0ull;
-    if (const char *e = getenv("FMX_GROUP_REFINE_MIN")) ix->group_refine_min = strtoull(e, nullptr, 10);
-    if (const char *e = getenv("FMX_GROUP_REFINE")) if (e[0] == '0') ix->group_refine_min = ~0ull;
-    if (const char *e = getenv("FMX_GROUP_CHECK")) ix->group_check = e[0] == '1';
+    read_policy_env(ix);
     if ((options & FMX_OPT_DEEP_LUT) && S >= 2 && v.n > 0) {
         // the largest K with S^K * 2P <= budget, deeper than the blob's k;
         // budget: FMX_DEEP_LUT_MB, else 160 GiB capped at half the free HBM
@@ -1274,11 +1282,6 @@ fmx_status fmx_locate_group_async(fmx_index *ix, const fmx_locate_job *jobs, uin
         }
         if (grps[0].n == 0) continue;
         const uint32_t ngroups = grps[ng].n ? ng + 1 : ng;
-        // (A/B) the persistent grid's tile counter: batch 0's workspace header
-        if (ngroups == 1 && ix->search_persistent && ix->occ_mode == FMX_OCC_INTERLEAVED && !ix->qa.dlut &&
-            !ix->qa.safull && !ix->qa.text)
-            grps[0].tile_ctr =
-                reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(grps[0].b[0].tiles) - kWsHeader);
         const fmx_status st = dev_err(timed_split(ix, "locate", "locate.search", "locate.emit", s, units,
                                                   [&](hipEvent_t mid) {
             return launch_locate_groups(ix, grps.get(), ngroups, stage, status, s, mid);
@@ -1364,7 +1367,9 @@ fmx_status fmx_count_batch(fmx_index *ix, const uint8_t *bytes, const uint64_t *
     return read_status(ix, s);
 }
 
-// The host-API locate workspace lives in the index, zeroed when (re)allocated.
+// The host-API locate workspace lives in the index.  Not initialised: every
+// launch writes each workspace word it reads (a grouped launch zeroes its own
+// key counters; the fused hand-off words count only under the launch's tag).
 static fmx_status ensure_ws(fmx_index *ix, uint64_t n) {
     const uint64_t need = ws_bytes_for(ix, n);
     if (ix->ws_bytes >= need) return FMX_OK;
@@ -1373,12 +1378,6 @@ static fmx_status ensure_ws(fmx_index *ix, uint64_t n) {
     ix->ws_bytes = 0;
     const uint64_t want = std::max<uint64_t>(need, 1 << 16);
     if (hipMalloc(&ix->d_ws, want) != hipSuccess) return FMX_E_DEVICE;
-    // zeroed on the index's own (non-blocking) stream, which the host-API
-    // launches use (a plain hipMemset runs on the null stream, unordered with
-    // it); only the persistent-grid A/B variant's tile counter needs it (a
-    // grouped launch zeroes its own key counters)
-    if (hipMemsetAsync(ix->d_ws, 0, want, ix->stream) != hipSuccess) return FMX_E_DEVICE;
-    if (hipStreamSynchronize(ix->stream) != hipSuccess) return FMX_E_DEVICE;
     ix->ws_bytes = want;
     return FMX_OK;
 }

@@ -117,13 +117,13 @@ constexpr uint8_t kNoDigit = 0xFF;
 #define FMX_OCC_WALK_DEFAULT 1
 #endif
 constexpr bool kOccWalkDefault = FMX_OCC_WALK_DEFAULT != 0;
-constexpr uint32_t kOccRecWalkBit = 4;
+constexpr uint32_t kOccRecWalkBit = 4;  // = kRecWalk (fmx_device.hpp), for the host code that does not include it
 // A one-row search result is located from the search's latest sampled row
 // when it has one (fmx_device.hpp SampledRow; build option for A/B: 0 walks
 // the final row as the reference does)
 #ifndef FMX_SAMPLED_ROW
 #define FMX_SAMPLED_ROW 1
-#endif  // = kRecWalk (fmx_device.hpp), for the host code that does not include it
+#endif
 constexpr uint32_t kStatusSlots = 1024;   // status words per index (one per stream)
 constexpr uint64_t kKmerLdsMax = 4096;    // k-mer count tables up to this size are staged in LDS
 
@@ -220,9 +220,8 @@ struct fmx_index {
     uint32_t rec_bytes = 0;
     uint32_t *d_status = nullptr;  // kStatusSlots words: one per stream launched on
     // per status slot, kMaxGroup ticket counters for the fused launches on its stream (take_ticket:
-    // zero between launches); FMX_FUSED_TICKETS=0 (A/B): workgroup index order instead
+    // zero between launches)
     uint32_t *d_tickets = nullptr;
-    bool fused_tickets = true;
     uint32_t *h_status = nullptr;               // pinned: kStatusSlots words (read_status)
     std::unique_ptr<std::mutex[]> slot_mu;      // one per status slot (read_status)
     std::vector<fmx::StatusSlot> slots;                   // kStatusSlots
@@ -230,47 +229,29 @@ struct fmx_index {
     std::vector<uint32_t> free_slots;
     uint64_t status_clock = 0;
     bool status_pressure = false;  // most words assigned: launches record completion events
-    bool search_persistent = false;  // FMX_SEARCH_PERSISTENT=1: k_search on a resident-sized grid (A/B)
-    // grouped launches (fmx::kWsHeader): launches of at least grouped_min
-    // patterns on the faithful index — by default 2^20 when the key spans
-    // at least 5 symbols (finish_load), FMX_GROUPED_MIN sets it, FMX_GROUPED=1
-    // groups every launch that can be, FMX_GROUPED=0 none; the key = the last
-    // gkey_len symbols, digits over the gkey_base symbols that occur in the text
-    uint64_t grouped_min = 0;
+    // grouped launches (fmx::kWsHeader): the key = a pattern's last gkey_len symbols, digits over the
+    // gkey_base symbols that occur in the text
+    uint32_t gkey_len = 0, gkey_base = 0;
     // launches of this index by path (fmx_index_info): grouped (packed / id-only records) and in
     // launch order — the tests assert which path a launch took
     mutable std::atomic<uint64_t> launches_grouped{0}, launches_grouped_raw{0}, launches_ordered{0};
-    uint32_t gkey_len = 0, gkey_base = 0;
-    uint32_t grouped_xcd = 0;  // each XCD searches one eighth of the key order (default; FMX_GROUPED_XCD=0 off)
-    uint32_t grouped_pair = 0; // FMX_GROUPED_PAIR=1: two patterns per lane in the grouped search
-    // the grouped search sorts each workgroup's 256 patterns by their next symbols after the key
-    // (k_search_grouped; default on, FMX_GROUPED_WSORT=0 off)
-    bool grouped_wsort = true;
-    bool grouped_raw = false;  // FMX_GROUPED_RAW=1: id-only sorted records even for patterns that pack (A/B)
-    uint64_t grouped_raw_min = ~0ull;  // launches needing id-only records: grouped from this many (default never)
-    // grouped launches of at least this many patterns re-sort each key's run by the next gkey_len
-    // symbols (k_group_refine; default never — measured even on C2 —, FMX_GROUP_REFINE_MIN sets it,
-    // FMX_GROUP_REFINE=0: never)
-    uint64_t group_refine_min = ~0ull;
-    // FMX_GROUP_CHECK=1 (debug): every grouped launch checks its sorted order before the search —
-    // each pattern placed exactly once, under its own key, with its own symbols (k_group_check_*)
-    bool group_check = false;
-    // launches in launch order run as one kernel (k_locate: search, then offsets and locations) when
-    // every batch has at most kFoldTiles tiles, the fixed-length hint and patterns of at most
-    // kFusedMaxLen symbols, and the launch has at most fused_max_tiles tiles (FMX_FUSED=0: never;
-    // FMX_FUSED_MAX_TILES); fused_late_ticks bounds its waits (FMX_FUSED_TIMEOUT_MS, 100 MHz ticks)
-    bool fused = true;
-    uint64_t fused_max_tiles = ~0ull;
-    uint64_t fused_late_ticks = 0;
-    mutable std::atomic<uint64_t> launches_fused{0};  // (a subset of launches_ordered)
-    // FMX_EMIT_CHAIN=1 (A/B): grouped launches end with k_emit_chain (tile counts handed from tile to tile,
-    // as k_locate) instead of k_group_tiles + k_emit, when every batch has at most kFoldTiles tiles
-    // (680 vs 235 us per C2 launch: the polls of ~2,000 short resident workgroups, profiles/r5/r5w_chain_*)
-    bool emit_chain = false;
-    // k_emit sums the earlier tiles' counts itself for batches of at most kFoldTiles tiles in launch order;
-    // grouped launches run k_scan first (-1: that policy; FMX_EMIT_FOLD=1 / 0: fold / k_scan everywhere)
-    int emit_fold = -1;
+    mutable std::atomic<uint64_t> launches_fused{0};    // (a subset of launches_ordered)
     mutable std::atomic<uint64_t> launches_chained{0};  // (a subset of the grouped launches)
+    // Launch policy, set once at load from the environment: read_policy_env (fmx_api.cpp) lists every
+    // variable, its default and what it does.
+    uint64_t grouped_min = 0;            // launches of at least this many patterns are grouped
+    uint64_t grouped_raw_min = ~0ull;    // ... those needing id-only sorted records: from this many
+    bool grouped_raw = false;            // id-only sorted records even for patterns that pack
+    uint32_t grouped_xcd = 1;            // each XCD searches one eighth of the key order
+    bool grouped_wsort = true;           // k_search_grouped sorts each workgroup's patterns below the key
+    uint64_t group_refine_min = ~0ull;   // grouped launches from this many patterns run k_group_refine
+    bool group_check = false;            // every grouped launch checks its sorted order (k_group_check_*)
+    bool fused = true;                   // launches in launch order may run as one kernel (k_locate)
+    uint64_t fused_max_tiles = ~0ull;    // ... those of at most this many tiles
+    uint64_t fused_late_ticks = 0;       // bound on a fused launch's waits (wall-clock ticks)
+    bool fused_tickets = true;           // fused workgroups take their tile by ticket (d_tickets)
+    bool emit_chain = false;             // grouped launches end with k_emit_chain
+    int emit_fold = -1;                  // k_emit sums earlier tiles itself: 1 / 0 everywhere, -1 per path
     std::mutex status_mu;
     uint8_t *d_dlut = nullptr;
     uint64_t dlut_bytes = 0;
@@ -353,10 +334,6 @@ struct LocateGroup {
     // sorted position or a pattern id of the whole launch to its batch
     const struct GroupTab *gtab;
     uint32_t gn, vbase;
-    // FMX_SEARCH_PERSISTENT=1 (A/B): k_search runs a resident-sized grid whose
-    // workgroups take tiles from this counter (batch 0's workspace header,
-    // zero between launches: k_emit resets it); null = one workgroup per tile
-    uint32_t *tile_ctr;
     // k_locate / k_emit_chain: one ticket counter per batch (fmx_index::d_tickets, the launch's status
     // slot's kMaxGroup words; take_ticket); null = each workgroup answers the tile of its own index
     uint32_t *tickets;
@@ -371,7 +348,6 @@ inline void group_reset(LocateGroup &g) {
     g.gtotal = 0;
     g.gtab = nullptr;
     g.gn = g.vbase = 0;
-    g.tile_ctr = nullptr;
     g.tickets = nullptr;
 }
 // `mid` (optional): an event recorded between k_search and k_emit (timing).
@@ -417,7 +393,7 @@ constexpr uint32_t kEmitTiles = FMX_EMIT_TILES;
 // reads its patterns in order.
 // Locate workspace of a batch of n patterns (G = ceil(n / 256), R =
 // locate_rec_bytes):
-//   [256 B header][kGroupCounterRoom u32 key counters][tile counts: G][tile
+//   [256 B header][kGroupBins u32 key counters][tile counts: G][tile
 //   offsets: G][search records: n x R][its share of the sorted order: n x 16 B]
 // The counters sit at a fixed offset in batch 0's workspace; every grouped
 // launch zeroes them on its stream first (32 KB, a few microseconds), so no
@@ -437,19 +413,6 @@ constexpr uint32_t kGroupPackBits = 96;
 constexpr uint32_t kGroupedXcd = 1;  // k_search_grouped opts: deal the key order out XCD by XCD
 constexpr uint32_t kWsortBytes = 1024 + 256 * 16;  // its in-workgroup sort's LDS (256 counters, 256 records)
 constexpr uint32_t kGroupRawStage = 216;  // raw records: patterns up to this long are staged in LDS by the search
-// Build option (A/B): each key's run of the sorted order split into
-// kGroupSlots sub-runs, one per slot = chunk mod kGroupSlots (8: the XCD that
-// places the chunk, under the round-robin placement of workgroups), so that
-// an XCD's scattered 16-B record writes would fill whole lines in its L2.
-// Measured slower at 8 (C2: place 894 vs 566 us, count 229 vs 157 us per
-// group, 3.85 vs 4.01e9; profiles/r5/r5sab_*): the place pass is not bound
-// by partial-line writes.  Counters key-major: key k, slot s at
-// k * kGroupSlots + s.
-#ifndef FMX_GROUP_SLOTS
-#define FMX_GROUP_SLOTS 1
-#endif
-constexpr uint32_t kGroupSlots = FMX_GROUP_SLOTS;
-constexpr uint32_t kGroupCounterRoom = kGroupBins * kGroupSlots;
 // Batches per grouped launch: up to kMaxMega, as several LocateGroups of at
 // most kMaxGroup (kernel arguments) whose key, place, tile and emit kernels run
 // per group and whose count scan, refine and search run once over the whole
@@ -483,7 +446,7 @@ struct GroupTab {
     void *sorted[kMaxMega];  // = desc[j].sorted, compact for the place pass's staging (64 lines, not 256)
     GroupDesc desc[kMaxMega];
 };
-constexpr uint64_t kWsGroupTab = 256 + 4ull * kGroupCounterRoom;  // (16-B aligned)
+constexpr uint64_t kWsGroupTab = 256 + 4ull * kGroupBins;  // (16-B aligned)
 constexpr uint64_t kWsHeader = kWsGroupTab + ((sizeof(GroupTab) + 15) & ~15ull);
 inline uint64_t group_chunks(uint64_t n) { return ((n + 255) / 256 + kGroupChunkTiles - 1) / kGroupChunkTiles; }
 
@@ -501,7 +464,7 @@ struct LayoutOps {
     // grouped launch (faithful variant): k_search_grouped over `total` patterns in key order;
     // opts = kGroupedXcd | wsort << 8 (k_search_grouped)
     hipError_t (*search_grouped)(const QueryArgs &qa, uint32_t vb, uint32_t rec, const LocateGroup &grp,
-                                 uint64_t total, uint32_t cap, uint32_t pair, uint32_t opts, hipStream_t s);
+                                 uint64_t total, uint32_t cap, uint32_t opts, hipStream_t s);
     hipError_t (*dlut_level)(const QueryArgs &qa, uint32_t vb, uint32_t rec, const void *parent, uint64_t np,
                              void *child, hipStream_t s);
     hipError_t (*full_sa)(const QueryArgs &qa, uint32_t vb, uint32_t rec, uint64_t n, void *sa_out,

@@ -77,44 +77,33 @@ __device__ __forceinline__ uint64_t block_excl_scan(uint64_t v, uint64_t *total,
 // aligned vectors, up to four per thread in flight (an aligned vector holding
 // at least one byte of the batch never leaves the batch's page).  Returns
 // false if the tile does not fit; the patterns are then read from HBM.
-// NP patterns per thread (a pair of tiles: NP = 2): thread t stages and
-// later searches patterns first + t, first + 256 + t, ... of one span.
-template <typename P, int NP>
-__device__ __forceinline__ bool stage_span(const Tables<P> &s, uint8_t *s_pat, const uint8_t *bytes,
-                                           const uint64_t *offs, uint64_t npat, uint64_t first, bool rev,
-                                           uint32_t stage_bytes, uint32_t stride, uint32_t *status,
-                                           uint64_t *beg, uint64_t *end, uint64_t &b0, uint64_t &b1) {
-    const uint64_t last = first + 256 * NP < npat ? first + 256 * NP : npat;
-    uint64_t chk[NP];
+template <typename P>
+__device__ __forceinline__ bool stage_patterns(const Tables<P> &s, uint8_t *s_pat, const uint8_t *bytes,
+                                               const uint64_t *offs, uint64_t npat, uint64_t first, bool rev,
+                                               uint32_t stage_bytes, uint32_t stride, uint32_t *status,
+                                               uint64_t &beg, uint64_t &end, uint64_t &b0, uint64_t &b1) {
+    const uint64_t last = first + 256 < npat ? first + 256 : npat;
+    const uint64_t i = first + threadIdx.x;
+    uint64_t chk;
     if (stride) {
         // FMX_HINT_FIXED_LEN: offs[i] == i * stride, so the byte loads need
-        // not wait for the offsets; each thread's own end offsets are loaded
-        // alongside them and checked once they have arrived.
+        // not wait for the offsets; each thread's own end offset is loaded
+        // alongside them and checked once it has arrived.
         b0 = first * stride;
         b1 = last * stride;
-#pragma unroll
-        for (int q = 0; q < NP; ++q) {
-            const uint64_t i = first + 256 * q + threadIdx.x;
-            beg[q] = i < npat ? i * stride : 0;
-            end[q] = i < npat ? beg[q] + stride : 0;
-            chk[q] = i < npat ? offs[i + 1] : 0;
-        }
+        beg = i < npat ? i * stride : 0;
+        end = i < npat ? beg + stride : 0;
+        chk = i < npat ? offs[i + 1] : 0;
         if (first == 0 && threadIdx.x == 0 && offs[0] != 0) atomicOr(status, kStatusStride);
     } else {
         b0 = offs[first];
         b1 = offs[last];
-#pragma unroll
-        for (int q = 0; q < NP; ++q) {
-            const uint64_t i = first + 256 * q + threadIdx.x;
-            beg[q] = i < npat ? offs[i] : 0;
-            end[q] = i < npat ? offs[i + 1] : 0;
-            chk[q] = end[q];
-        }
+        beg = i < npat ? offs[i] : 0;
+        end = i < npat ? offs[i + 1] : 0;
+        chk = end;
     }
     const uint64_t len = b1 - b0;
-    uint32_t bad_stride = 0;
-#pragma unroll
-    for (int q = 0; q < NP; ++q) bad_stride |= chk[q] != end[q];
+    const uint32_t bad_stride = chk != end;
     // the encoding table (stage_tables, written by every thread) is read below
     __syncthreads();
     if (len > stage_bytes) {
@@ -150,15 +139,6 @@ __device__ __forceinline__ bool stage_span(const Tables<P> &s, uint8_t *s_pat, c
     }
     if (bad_stride) atomicOr(status, kStatusStride);
     return true;
-}
-
-template <typename P>
-__device__ __forceinline__ bool stage_patterns(const Tables<P> &s, uint8_t *s_pat, const uint8_t *bytes,
-                                               const uint64_t *offs, uint64_t npat, uint64_t first, bool rev,
-                                               uint32_t stage_bytes, uint32_t stride, uint32_t *status,
-                                               uint64_t &beg, uint64_t &end, uint64_t &b0, uint64_t &b1) {
-    return stage_span<P, 1>(s, s_pat, bytes, offs, npat, first, rev, stage_bytes, stride, status, &beg, &end, b0,
-                            b1);
 }
 
 template <typename P>
@@ -391,32 +371,6 @@ __global__ __launch_bounds__(256, VAR == kVarDerivedLong ? 4 : 8) void k_search(
     __shared__ uint64_t s_scan[4];
     stage_tables(a, s, s_pat + stage_bytes);
     search_tile<P, N, VB, REC, VAR>(a, grp, s, s_pat, s_scan, stage_bytes, blockIdx.x);
-}
-
-// The same on a resident-sized grid (FMX_SEARCH_PERSISTENT=1, A/B): each
-// workgroup stages the tables once, then takes 256-pattern tiles from an
-// atomic counter until none is left; no workgroup waits on another.
-template <typename P, int N, int VB, int REC, int VAR>
-__global__ __launch_bounds__(256, VAR == kVarDerivedLong ? 4 : 8) void k_search_tiles(const QueryArgs a,
-                                                                                      const LocateGroup grp,
-                                                                                      uint32_t stage_bytes,
-                                                                                      uint32_t tiles) {
-    __shared__ Tables<P> s;
-    FMX_DYN_LDS(s_pat);  // stage_bytes, then the k-mer table (dynamic)
-    __shared__ uint64_t s_scan[4];
-    __shared__ uint32_t s_tile;
-    stage_tables(a, s, s_pat + stage_bytes);
-    // Bounded, with a wave-uniform (scalar) exit: an unbounded for (;;) whose
-    // only exit was a branch on the LDS value hung on the GPU (the compiler
-    // cannot prove that branch uniform around the barriers).
-    for (uint32_t it = 0; it < tiles; ++it) {
-        if (threadIdx.x == 0) s_tile = atomicAdd(grp.tile_ctr, 1u);
-        __syncthreads();  // (also publishes the tables on the first pass)
-        const uint32_t vt = __builtin_amdgcn_readfirstlane(s_tile);
-        if (vt >= tiles) break;
-        // (search_tile's closing barriers order every read of s_tile before the next write)
-        search_tile<P, N, VB, REC, VAR>(a, grp, s, s_pat, s_scan, stage_bytes, vt);
-    }
 }
 
 // ------------------------------------------- k_locate (search + emit, fused)
@@ -662,16 +616,12 @@ __global__ __launch_bounds__(1024, W <= 8 ? 2 : 1) void k_group_key(const QueryA
     // global adds for all of them; measured no faster than one, r4w: the
     // atomics do not bound it), the place pass one
     constexpr uint32_t CPW = PLACE ? 1u : kCountChunks;
-    // the chunks' slot (kGroupSlots): the place pass's chunk is its workgroup; the count pass's
-    // workgroup w takes chunks of one slot, w mod S + S (CPW (w div S) + r), r < CPW
-    constexpr uint32_t S = kGroupSlots;
-    const uint32_t slot = blockIdx.x % S;
     uint32_t key_r[PPT], rank_r[PPT];
     U4 rec_r[PLACE ? PPT : 1];
     uint64_t pfirst = 0, pn = 0;  // (the place pass's one chunk, after the loop)
 #pragma unroll
     for (uint32_t r = 0; r < CPW; ++r) {
-    const uint32_t c = PLACE ? blockIdx.x : (blockIdx.x / S) * (S * CPW) + r * S + slot;
+    const uint32_t c = PLACE ? blockIdx.x : blockIdx.x * CPW + r;
     if constexpr (!PLACE) {
         const uint32_t nchunks = grp.chunk_begin[grp.n - 1] +
                                  (uint32_t)(((grp.b[grp.n - 1].npat + 255) / 256 + kGroupChunkTiles - 1) /
@@ -758,7 +708,7 @@ __global__ __launch_bounds__(1024, W <= 8 ? 2 : 1) void k_group_key(const QueryA
 #pragma unroll
         for (uint32_t u = 0; u < per; ++u) {
             const uint32_t h = hist[u * T + t];
-            if (h) atomicAdd(grp.gcount + (u * T + t) * S + slot, h);
+            if (h) atomicAdd(grp.gcount + (u * T + t), h);
         }
         return;
     } else {
@@ -767,7 +717,7 @@ __global__ __launch_bounds__(1024, W <= 8 ? 2 : 1) void k_group_key(const QueryA
 #pragma unroll
         for (uint32_t u = 0; u < per; ++u) h[u] = hist[u * T + t];
 #pragma unroll
-        for (uint32_t u = 0; u < per; ++u) base[u] = h[u] ? atomicAdd(grp.gcount + (u * T + t) * S + slot, h[u]) : 0u;
+        for (uint32_t u = 0; u < per; ++u) base[u] = h[u] ? atomicAdd(grp.gcount + (u * T + t), h[u]) : 0u;
 #pragma unroll
         for (uint32_t u = 0; u < per; ++u) hist[u * T + t] = base[u];  // the chunk's first position per key
         __syncthreads();
@@ -837,8 +787,7 @@ __global__ __launch_bounds__(1024) void k_group_refine(const QueryArgs a, const 
     }
     __syncthreads();
     for (uint32_t k = blockIdx.x; k < kGroupBins; k += gridDim.x) {
-    // (key k's run: its slots' sub-runs, one after another)
-    uint64_t end = grp.gcount[k * kGroupSlots + kGroupSlots - 1], beg = k ? grp.gcount[k * kGroupSlots - 1] : 0;
+    uint64_t end = grp.gcount[k], beg = k ? grp.gcount[k - 1] : 0;
     end = end < total ? end : total;
     beg = beg < end ? beg : end;
     if (end - beg < 2) continue;  // (workgroup-uniform)
@@ -911,11 +860,10 @@ __global__ __launch_bounds__(1024) void k_group_refine(const QueryArgs a, const 
 
 
 // 3. Search the launch's patterns in key order: workgroup b takes sorted
-// positions [256 K b, 256 K (b + 1)), K = 1 or 2 patterns per lane (lane t:
-// positions 256 K b + t + 256 j) — their records are read in order, the
-// symbols unpacked into cap bytes of LDS per pattern — searches (K = 2: both
-// chains in lockstep, search_pair), walks a single row, and leaves each
-// record at its pattern's own index.
+// positions [256 b, 256 (b + 1)), one pattern per lane — their records are
+// read in order, the symbols unpacked into cap bytes of LDS per pattern —
+// searches, walks a single row, and leaves each record at its pattern's own
+// index.
 template <typename P>
 __device__ __forceinline__ void grouped_unpack(const U4 &e, uint32_t m, uint32_t bits, uint8_t *dst) {
     const uint32_t msk = (1u << bits) - 1u;
@@ -936,12 +884,12 @@ __device__ __forceinline__ void grouped_unpack(const U4 &e, uint32_t m, uint32_t
 // The LDS before the k-mer table: each lane's cap bytes of symbols, or the
 // in-workgroup sort's room when that is larger (it is done with before the
 // symbols are unpacked).
-__host__ __device__ constexpr uint32_t grouped_pat_bytes(uint32_t k, uint32_t cap, uint32_t wsort) {
-    return 256u * k * cap > kWsortBytes || !wsort ? 256u * k * cap : kWsortBytes;
+__host__ __device__ constexpr uint32_t grouped_pat_bytes(uint32_t cap, uint32_t wsort) {
+    return 256u * cap > kWsortBytes || !wsort ? 256u * cap : kWsortBytes;
 }
 
 // opts bit 0 (kGroupedXcd): the XCD deal below; bits 8-15 = wsort: a full
-// workgroup of packed records (K = 1) first sorts its 256 patterns by their
+// workgroup of packed records first sorts its 256 patterns by their
 // next wsort symbols after the first opts >> 16 last symbols — those the
 // sorted order is already ordered by: the key's, or with the refine pass
 // twice as many (digits over the key's base, the nearest
@@ -951,10 +899,9 @@ __host__ __device__ constexpr uint32_t grouped_pat_bytes(uint32_t k, uint32_t ca
 // (one request each) instead of up to 64 different ones.  Which lane answers
 // which pattern changes nothing in the results (each is written at its own
 // index).
-template <typename P, int N, int VB, int REC, int K>
-__global__ __launch_bounds__(256, K == 2 ? 6 : 8) void k_search_grouped(const QueryArgs a, const LocateGroup grp,
-                                                           uint64_t total, uint32_t cap, uint32_t opts) {
-    static_assert(K == 1 || K == 2, "one or two patterns per lane");
+template <typename P, int N, int VB, int REC>
+__global__ __launch_bounds__(256, 8) void k_search_grouped(const QueryArgs a, const LocateGroup grp, uint64_t total,
+                                                           uint32_t cap, uint32_t opts) {
     __shared__ Tables<P> s;
     __shared__ uint8_t s_dig[kMaxSigma + 1];  // (wsort) symbol -> digit; sigma (past the pattern's start) -> 0
     __shared__ uint64_t s_wscan[4];
@@ -962,10 +909,10 @@ __global__ __launch_bounds__(256, K == 2 ? 6 : 8) void k_search_grouped(const Qu
     // before each (32-bit: a launch's are), and each one's pattern length
     __shared__ uint32_t s_first[kMaxMega], s_vfirst[kMaxMega];
     __shared__ uint16_t s_stride[kMaxMega];
-    const uint32_t wsort = K == 1 && !grp.graw ? (opts >> 8) & 0xffu : 0u, xcd = opts & kGroupedXcd;
+    const uint32_t wsort = !grp.graw ? (opts >> 8) & 0xffu : 0u, xcd = opts & kGroupedXcd;
     const uint32_t wskip = opts >> 16;
-    FMX_DYN_LDS(s_pat);  // 256 K x cap B of symbols (cap >= every batch's length), then the k-mer table
-    stage_tables(a, s, s_pat + grouped_pat_bytes(K, cap, wsort));
+    FMX_DYN_LDS(s_pat);  // 256 x cap B of symbols (cap >= every batch's length), then the k-mer table
+    stage_tables(a, s, s_pat + grouped_pat_bytes(cap, wsort));
     if (threadIdx.x <= (uint32_t)kMaxSigma)
         s_dig[threadIdx.x] =
             threadIdx.x < a.sigma && a.tab->dig[threadIdx.x] != kNoDigit ? a.tab->dig[threadIdx.x] : 0;
@@ -984,132 +931,91 @@ __global__ __launch_bounds__(256, K == 2 ? 6 : 8) void k_search_grouped(const Qu
         const uint32_t q = gridDim.x / 8, rem = gridDim.x % 8, x = blockIdx.x % 8;
         chunk = x * q + (x < rem ? x : rem) + blockIdx.x / 8;
     }
-    PatView pv[K];
-    bool live[K];
-    uint64_t pi[K];
-    uint8_t *recp[K];
-#pragma unroll
-    for (int q = 0; q < K; ++q) {
-        const uint64_t sp = (uint64_t)chunk * (256u * K) + (uint32_t)q * 256u + threadIdx.x;
-        live[q] = sp < total;
-        pi[q] = 0;
-        recp[q] = nullptr;
-        uint8_t *dst = s_pat + ((uint32_t)q * 256u + threadIdx.x) * cap;
-        pv[q].m = 0;
-        pv[q].rev = false;
-        pv[q].raw = nullptr;
-        pv[q].enc = s.enc;
-        pv[q].sym = dst;
-        if (!live[q]) continue;
-        const uint32_t js = lds_upper(s_first, grp.gn, (uint32_t)sp);
-        U4 e = reinterpret_cast<const U4 *>(gt.desc[js].sorted)[sp - s_first[js]];
-        if (K == 1 && wsort && (uint64_t)chunk * 256u + 256u <= total) {  // (workgroup-uniform: all lanes live)
-            uint32_t *hist = reinterpret_cast<uint32_t *>(s_pat);
-            U4 *stage = reinterpret_cast<U4 *>(s_pat + 1024);
-            const uint32_t t = threadIdx.x, base = grp.gkey_base;
-            const uint32_t m = s_stride[lds_upper(s_vfirst, grp.gn, e.w)];
-            uint32_t k2 = 0;
-            for (uint32_t d = 0; d < wsort; ++d) {
-                const uint32_t back = wskip + d;  // 0 = the pattern's last symbol
-                k2 = k2 * base + s_dig[back < m ? packed_sym(e, m - 1 - back, grp.gbits) : a.sigma];
-            }
-            hist[t] = 0;
-            __syncthreads();
-            const uint32_t rank = atomicAdd(&hist[k2], 1u);
-            __syncthreads();
-            uint64_t agg;
-            const uint32_t before = (uint32_t)block_excl_scan(hist[t], &agg, s_wscan);
-            hist[t] = before;  // (each thread its own counter; read after the next barrier)
-            __syncthreads();
-            stage[hist[k2] + rank] = e;
-            __syncthreads();
-            e = stage[t];
-            __syncthreads();  // (the stage is s_pat: every lane has its record before any unpacks)
+    const uint64_t sp = (uint64_t)chunk * 256u + threadIdx.x;
+    if (sp >= total) return;  // (a workgroup that sorts below is full: every lane reaches its barriers)
+    uint8_t *dst = s_pat + threadIdx.x * cap;
+    PatView pv;
+    pv.m = 0;
+    pv.rev = false;
+    pv.raw = nullptr;
+    pv.enc = s.enc;
+    pv.sym = dst;
+    const uint32_t js = lds_upper(s_first, grp.gn, (uint32_t)sp);
+    U4 e = reinterpret_cast<const U4 *>(gt.desc[js].sorted)[sp - s_first[js]];
+    if (wsort && (uint64_t)chunk * 256u + 256u <= total) {  // (workgroup-uniform: all lanes live)
+        uint32_t *hist = reinterpret_cast<uint32_t *>(s_pat);
+        U4 *stage = reinterpret_cast<U4 *>(s_pat + 1024);
+        const uint32_t t = threadIdx.x, base = grp.gkey_base;
+        const uint32_t m = s_stride[lds_upper(s_vfirst, grp.gn, e.w)];
+        uint32_t k2 = 0;
+        for (uint32_t d = 0; d < wsort; ++d) {
+            const uint32_t back = wskip + d;  // 0 = the pattern's last symbol
+            k2 = k2 * base + s_dig[back < m ? packed_sym(e, m - 1 - back, grp.gbits) : a.sigma];
         }
-        const uint32_t v = e.w;
-        const uint32_t jb = lds_upper(s_vfirst, grp.gn, v);
-        const GroupDesc &dj = gt.desc[jb];  // (recs: written at the end; bytes, rev: id-only records)
-        recp[q] = dj.recs;
-        pi[q] = (uint64_t)(v - s_vfirst[jb]);
-        pv[q].m = s_stride[jb];
-        if (grp.graw) {
-            const uint32_t m = s_stride[jb];
-            const uint8_t *src = dj.bytes + pi[q] * m;
-            if (cap >= m) {
-                // the pattern's bytes (input order) into its cap bytes of LDS,
-                // encoded, in pattern order: aligned 16-B vectors, four in
-                // flight per round trip (grp.graw with m <= kGroupRawStage)
-                const uint64_t a = reinterpret_cast<uint64_t>(src), a0 = a & ~15ull;
-                const uint32_t lead = (uint32_t)(a - a0), nv = (lead + m + 15) >> 4;
-                const bool rv = dj.rev != 0;
-                const U4 *vp = reinterpret_cast<const U4 *>(a0);
-                for (uint32_t v0 = 0; v0 < nv; v0 += 4) {
-                    U4 x[4];
+        hist[t] = 0;
+        __syncthreads();
+        const uint32_t rank = atomicAdd(&hist[k2], 1u);
+        __syncthreads();
+        uint64_t agg;
+        const uint32_t before = (uint32_t)block_excl_scan(hist[t], &agg, s_wscan);
+        hist[t] = before;  // (each thread its own counter; read after the next barrier)
+        __syncthreads();
+        stage[hist[k2] + rank] = e;
+        __syncthreads();
+        e = stage[t];
+        __syncthreads();  // (the stage is s_pat: every lane has its record before any unpacks)
+    }
+    const uint32_t v = e.w;
+    const uint32_t jb = lds_upper(s_vfirst, grp.gn, v);
+    const GroupDesc &dj = gt.desc[jb];  // (recs: written at the end; bytes, rev: id-only records)
+    uint8_t *const recp = dj.recs;
+    const uint64_t pi = (uint64_t)(v - s_vfirst[jb]);
+    pv.m = s_stride[jb];
+    if (grp.graw) {
+        const uint32_t m = s_stride[jb];
+        const uint8_t *src = dj.bytes + pi * m;
+        if (cap >= m) {
+            // the pattern's bytes (input order) into its cap bytes of LDS,
+            // encoded, in pattern order: aligned 16-B vectors, four in
+            // flight per round trip (grp.graw with m <= kGroupRawStage)
+            const uint64_t a = reinterpret_cast<uint64_t>(src), a0 = a & ~15ull;
+            const uint32_t lead = (uint32_t)(a - a0), nv = (lead + m + 15) >> 4;
+            const bool rv = dj.rev != 0;
+            const U4 *vp = reinterpret_cast<const U4 *>(a0);
+            for (uint32_t v0 = 0; v0 < nv; v0 += 4) {
+                U4 x[4];
 #pragma unroll
-                    for (uint32_t u = 0; u < 4; ++u)
-                        if (v0 + u < nv) x[u] = vp[v0 + u];
+                for (uint32_t u = 0; u < 4; ++u)
+                    if (v0 + u < nv) x[u] = vp[v0 + u];
 #pragma unroll
-                    for (uint32_t u = 0; u < 4; ++u) {
-                        if (v0 + u >= nv) continue;
+                for (uint32_t u = 0; u < 4; ++u) {
+                    if (v0 + u >= nv) continue;
 #pragma unroll
-                        for (uint32_t w = 0; w < 16; ++w) {
-                            const uint32_t pos = 16u * (v0 + u) + w - lead;  // (wraps below 0: skipped)
-                            if (pos < m) dst[rv ? m - 1 - pos : pos] = s.enc[(x[u][w >> 2] >> (8 * (w & 3))) & 0xffu];
-                        }
+                    for (uint32_t w = 0; w < 16; ++w) {
+                        const uint32_t pos = 16u * (v0 + u) + w - lead;  // (wraps below 0: skipped)
+                        if (pos < m) dst[rv ? m - 1 - pos : pos] = s.enc[(x[u][w >> 2] >> (8 * (w & 3))) & 0xffu];
                     }
                 }
-            } else {  // longer than the LDS room: the bytes from HBM, encoded on each access
-                pv[q].raw = src;
-                pv[q].rev = dj.rev != 0;
-                pv[q].sym = nullptr;
             }
-        } else {
-            grouped_unpack<P>(e, s_stride[jb], grp.gbits, dst);
-        }
-    }
-    P lo_r[K], hi_r[K], rloc[K];
-    uint64_t mask[K];
-    uint32_t mode[K];
-    if constexpr (K == 1) {
-        if (!live[0]) return;
-        SampledRow<P> smp;
-        const uint32_t bad = search<P, N, VB, REC, kVarFaithful>(a, s, pv[0], lo_r[0], hi_r[0], rloc[0], mask[0],
-                                                                  mode[0], &smp);
-        if (bad) atomicOr(a.status, bad);
-        if (mode[0] == kHitRows && hi_r[0] - lo_r[0] == P(1)) {
-            rloc[0] = locate_one<P, N, VB, REC>(a, s.C, lo_r[0], smp);
-            mode[0] = kHitOne;
+        } else {  // longer than the LDS room: the bytes from HBM, encoded on each access
+            pv.raw = src;
+            pv.rev = dj.rev != 0;
+            pv.sym = nullptr;
         }
     } else {
-        uint32_t bad[2];
-        search_pair<P, N, VB, REC>(a, s, pv, live, lo_r, hi_r, bad);
-        if (bad[0] | bad[1]) atomicOr(a.status, bad[0] | bad[1]);
-        bool one[2];
-        P row[2];
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            mode[q] = kHitRows;
-            mask[q] = 0;
-            rloc[q] = 0;
-            one[q] = live[q] && hi_r[q] - lo_r[q] == P(1);
-            row[q] = lo_r[q];
-        }
-        if (one[0] || one[1]) {
-            P loc[2];
-            walk_pair<P, N, VB, REC>(a, s.C, row, one, loc);
-#pragma unroll
-            for (int q = 0; q < 2; ++q)
-                if (one[q]) {
-                    rloc[q] = loc[q];
-                    mode[q] = kHitOne;
-                }
-        }
+        grouped_unpack<P>(e, s_stride[jb], grp.gbits, dst);
     }
-#pragma unroll
-    for (int q = 0; q < K; ++q)
-        if (live[q])
-            reinterpret_cast<NarrowRec<P> *>(recp[q])[pi[q]] =
-                NarrowRec<P>{mode[q] == kHitOne ? rloc[q] : lo_r[q], (P)(hi_r[q] - lo_r[q])};
+    P lo, hi, rloc;
+    uint64_t mask;
+    uint32_t mode;
+    SampledRow<P> smp;
+    const uint32_t bad = search<P, N, VB, REC, kVarFaithful>(a, s, pv, lo, hi, rloc, mask, mode, &smp);
+    if (bad) atomicOr(a.status, bad);
+    if (mode == kHitRows && hi - lo == P(1)) {
+        rloc = locate_one<P, N, VB, REC>(a, s.C, lo, smp);
+        mode = kHitOne;
+    }
+    reinterpret_cast<NarrowRec<P> *>(recp)[pi] = NarrowRec<P>{mode == kHitOne ? rloc : lo, (P)(hi - lo)};
 }
 
 // This workgroup's batch of a k_group_tiles launch (workgroup-uniform).
@@ -1184,7 +1090,6 @@ __global__ __launch_bounds__(256) void k_emit(const QueryArgs a, const LocateGro
     }
     __syncthreads();  // (also publishes sC)
     uint64_t base = fold ? s_part[0] + s_part[1] + s_part[2] + s_part[3] : 0;
-    if (grp.tile_ctr && blockIdx.x == 0 && threadIdx.x == 0) *grp.tile_ctr = 0u;  // (k_search is done with it)
 #pragma unroll
     for (uint32_t k = 0; k < E; ++k) {
         const uint64_t g = g0 + k;

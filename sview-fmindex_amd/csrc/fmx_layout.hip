@@ -79,18 +79,7 @@ hipError_t disp(uint32_t vb, uint32_t rec, F &&f) {
                      uint32_t tiles, uint32_t sb, hipStream_t s) {
     return disp(vb, rec, [&]<int VB, int R>() {
         const uint32_t lds = sb + qa.kt_lds_bytes;
-        if (var == kVarFaithful && grp.tile_ctr) {
-            // resident-sized grid: workgroups per CU at this LDS size x CUs
-            int per_cu = 0, dev = 0, cus = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_search_tiles<P, N, VB, R, kVarFaithful>, 256,
-                                                             lds) != hipSuccess ||
-                hipGetDevice(&dev) != hipSuccess ||
-                hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-                return hipErrorInvalidValue;
-            const uint32_t grid = std::min<uint32_t>(tiles, (uint32_t)std::max(1, per_cu * cus));
-            hipLaunchKernelGGL((k_search_tiles<P, N, VB, R, kVarFaithful>), dim3(grid), dim3(256), lds, s, qa, grp, sb,
-                               tiles);
-        } else if (var == kVarFaithful) {
+        if (var == kVarFaithful) {
             hipLaunchKernelGGL((k_search<P, N, VB, R, kVarFaithful>), dim3(tiles), dim3(256), lds, s, qa, grp, sb);
         } else if constexpr (faithful_only(R)) {
             return hipErrorInvalidValue;
@@ -113,19 +102,12 @@ hipError_t disp(uint32_t vb, uint32_t rec, F &&f) {
 }
 
 [[maybe_unused]] hipError_t op_search_grouped(const QueryArgs &qa, uint32_t vb, uint32_t rec, const LocateGroup &grp,
-                                              uint64_t total, uint32_t cap, uint32_t pair, uint32_t opts,
-                                              hipStream_t s) {
+                                              uint64_t total, uint32_t cap, uint32_t opts, hipStream_t s) {
     return disp(vb, rec, [&]<int VB, int R>() {
-        const uint32_t per = pair ? 512u : 256u;
-        const uint64_t grid = (total + per - 1) / per;
+        const uint64_t grid = (total + 255) / 256;
         if (grid == 0 || grid > 0x7FFFFFFFull || cap == 0 || cap > kGroupRawStage) return hipErrorInvalidValue;
-        if (pair)
-            hipLaunchKernelGGL((k_search_grouped<P, N, VB, R, 2>), dim3((uint32_t)grid), dim3(256),
-                               grouped_pat_bytes(2, cap, 0) + qa.kt_lds_bytes, s, qa, grp, total, cap, opts & 0xffu);
-        else
-            hipLaunchKernelGGL((k_search_grouped<P, N, VB, R, 1>), dim3((uint32_t)grid), dim3(256),
-                               grouped_pat_bytes(1, cap, opts >> 8) + qa.kt_lds_bytes, s, qa, grp, total, cap,
-                               opts);
+        hipLaunchKernelGGL((k_search_grouped<P, N, VB, R>), dim3((uint32_t)grid), dim3(256),
+                           grouped_pat_bytes(cap, opts >> 8) + qa.kt_lds_bytes, s, qa, grp, total, cap, opts);
         return hipGetLastError();
     });
 }

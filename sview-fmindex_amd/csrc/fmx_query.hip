@@ -70,17 +70,17 @@ __global__ __launch_bounds__(256) void k_scan(const LocateGroup grp) {
 // ---------------------------------------------------------- grouped launches
 // (k_group_key<count / place> and k_search_grouped: fmx_kernels.hpp)
 
-// 2. The launch's key counts (per key and slot, key-major) -> each sub-run's
-// first sorted position (exclusive scan in place; 16 counters per thread per
-// pass, every load of a pass in flight at once).
+// 2. The launch's key counts -> each key's first sorted position (exclusive
+// scan in place; 16 counters per thread per pass, every load of a pass in
+// flight at once).
 __global__ __launch_bounds__(256) void k_group_scan(uint32_t *cnt) {
     __shared__ uint64_t s_scan[4];
     constexpr uint32_t per = 16;
     // whole passes only: a partial last pass would read and write past the
     // counters into the batch table that follows them
-    static_assert(kGroupCounterRoom % (256 * per) == 0, "kGroupCounterRoom must be a multiple of 4,096");
+    static_assert(kGroupBins % (256 * per) == 0, "kGroupBins must be a multiple of 4,096");
     uint32_t carry = 0;
-    for (uint32_t base = 0; base < kGroupCounterRoom; base += 256 * per) {
+    for (uint32_t base = 0; base < kGroupBins; base += 256 * per) {
         uint32_t v[per], sum = 0;
 #pragma unroll
         for (uint32_t u = 0; u < per; ++u) {
@@ -176,7 +176,7 @@ __global__ __launch_bounds__(256) void k_group_check_order(const QueryArgs a, co
     __syncthreads();
     const uint64_t sp = (uint64_t)blockIdx.x * 256u + t, total = grp.gtotal;
     if (sp >= total) return;
-    bool bad = grp.gcount[kGroupCounterRoom - 1] != total;  // (the last run ends at the launch's end)
+    bool bad = grp.gcount[kGroupBins - 1] != total;  // (the last run ends at the launch's end)
     const uint32_t js = lds_upper(gt.first, grp.gn, sp);
     const U4 e = reinterpret_cast<const U4 *>(gt.desc[js].sorted)[sp - gt.first[js]];
     const uint32_t jb = lds_upper(gt.vfirst, grp.gn, e.w);
@@ -192,7 +192,7 @@ __global__ __launch_bounds__(256) void k_group_check_order(const QueryArgs a, co
     uint32_t lo = 0, hi = kGroupBins - 1;
     while (lo < hi) {
         const uint32_t mid = (lo + hi) >> 1;
-        if ((uint64_t)grp.gcount[mid * kGroupSlots + kGroupSlots - 1] > sp) hi = mid;
+        if ((uint64_t)grp.gcount[mid] > sp) hi = mid;
         else lo = mid + 1;
     }
     const uint32_t m = B.stride;
@@ -511,7 +511,7 @@ static hipError_t launch_grouped(const fmx_index *ix, const QueryArgs &qa, Locat
     // the key counters start at zero whatever an earlier launch on this
     // workspace did, and the table is in place: both ordered
     // before the count pass on the stream
-    hipError_t e = hipMemsetAsync(gcount, 0, 4ull * kGroupCounterRoom, stream);
+    hipError_t e = hipMemsetAsync(gcount, 0, 4ull * kGroupBins, stream);
     if (e != hipSuccess) return e;
     // (vfirst, first32 and stride16 are contiguous: one upload of the three)
     static_assert(offsetof(GroupTab, first32) == offsetof(GroupTab, vfirst) + 4 * kMaxMega &&
@@ -529,9 +529,7 @@ static hipError_t launch_grouped(const fmx_index *ix, const QueryArgs &qa, Locat
     for (uint32_t g = 0; g < ng; ++g) {
         const uint32_t chunks = grps[g].chunk_begin[grps[g].n - 1] +
                                 (uint32_t)group_chunks(grps[g].b[grps[g].n - 1].npat);
-        // (workgroups of kCountChunks chunks of one slot each: kGroupSlots per kGroupSlots x kCountChunks chunks)
-        const uint32_t span = kGroupSlots * kCountChunks;
-        hipLaunchKernelGGL((k_group_key<5, false, true>), dim3((chunks + span - 1) / span * kGroupSlots),
+        hipLaunchKernelGGL((k_group_key<5, false, true>), dim3((chunks + kCountChunks - 1) / kCountChunks),
                            dim3(1024), 0, stream, qa, grps[g], rb);
     }
     if ((e = hipGetLastError()) != hipSuccess) return e;
@@ -572,18 +570,15 @@ static hipError_t launch_grouped(const fmx_index *ix, const QueryArgs &qa, Locat
     // each lane unpacks (or, raw, stages) its pattern into `cap` bytes of LDS: the longest batch's length,
     // 4-byte aligned (raw records longer than kGroupRawStage: the search reads the bytes from HBM, cap 4)
     if (raw && cap > kGroupRawStage) cap = 4;
-    // (two patterns per lane: packed records only — 512 lanes' staging would not fit LDS)
     // the in-workgroup sort's symbols: as many after those already in order (the key's, and the refine
     // pass's as many again) as base^w <= 256 allows (none when every pattern ends within them)
     const uint32_t sorted_len = ix->gkey_len * (refined ? 2u : 1u);
     uint32_t wsort = 0;
-    if (ix->grouped_wsort && !raw && !(ix->grouped_pair) && maxm > sorted_len)
+    if (ix->grouped_wsort && !raw && maxm > sorted_len)
         for (uint32_t w = 1, p = ix->gkey_base; p <= 256 && w <= 8 && w <= maxm - sorted_len; ++w, p *= ix->gkey_base)
             wsort = w;
     const uint32_t opts = (ix->grouped_xcd ? kGroupedXcd : 0u) | wsort << 8 | sorted_len << 16;
-    if ((e = d.ops->search_grouped(qa, d.vb, d.rec, grps[0], total, cap, ix->grouped_pair && !raw, opts,
-                                   stream)) != hipSuccess)
-        return e;
+    if ((e = d.ops->search_grouped(qa, d.vb, d.rec, grps[0], total, cap, opts, stream)) != hipSuccess) return e;
     if (!chain)
         for (uint32_t g = 0; g < ng; ++g) {
             const uint32_t ewg = set_emit_begin(grps[g]);
@@ -618,7 +613,6 @@ static bool is_grouped(const fmx_index *ix, const QueryArgs &qa, const LocateGro
                        uint64_t *total, uint32_t *bits, bool *raw) {
     uint64_t n = 0, tiles = 0;
     for (uint32_t g = 0; g < ng; ++g) {
-        if (grps[g].tile_ctr) return false;
         for (uint32_t j = 0; j < grps[g].n; ++j) n += grps[g].b[j].npat;
         tiles += group_tiles(grps[g]);
     }
@@ -649,7 +643,7 @@ static hipError_t launch_split(const fmx_index *ix, const QueryArgs &qa, LocateG
     }
     // in launch order, batches of at most kFoldTiles tiles of short fixed-length patterns: one kernel
     // (k_locate), unless the stream is being captured (a replayed graph would reuse the launch's tag)
-    bool fused = small && ix->fused && !grp.tile_ctr && tiles <= ix->fused_max_tiles;
+    bool fused = small && ix->fused && tiles <= ix->fused_max_tiles;
     for (uint32_t j = 0; fused && j < grp.n; ++j) fused = grp.b[j].stride != 0 && grp.b[j].stride <= kFusedMaxLen;
     if (fused && stream_capturing(stream)) fused = false;
     hipError_t e;

@@ -28,7 +28,7 @@ def grouped(request, monkeypatch):
     in-workgroup sort on) and with the refine sort and the device check on."""
     monkeypatch.setenv("FMX_GROUPED", "1")
     for k in ("FMX_GROUP_REFINE_MIN", "FMX_GROUP_REFINE", "FMX_GROUP_CHECK", "FMX_GROUPED_WSORT",
-              "FMX_GROUPED_RAW", "FMX_GROUPED_MIN", "FMX_GROUPED_PAIR", "FMX_GROUPED_XCD"):
+              "FMX_GROUPED_RAW", "FMX_GROUPED_MIN", "FMX_GROUPED_XCD"):
         monkeypatch.delenv(k, raising=False)
     if request.param == "refine_check":
         monkeypatch.setenv("FMX_GROUP_REFINE_MIN", "1")  # k_group_refine on every grouped launch, however small

@@ -232,8 +232,7 @@ def test_long_patterns_grouped_simt(pkg, O, simt, monkeypatch, m, pb, planes, vb
 
 
 GROUP_BINS = 8192  # fmx_internal.hpp kGroupBins
-GROUP_SLOTS = 1  # kGroupSlots (build option): key k's sub-run of slot s counts at k * GROUP_SLOTS + s
-COUNTERS = GROUP_BINS * GROUP_SLOTS
+COUNTERS = GROUP_BINS
 
 
 def test_group_check_catches_dirty_counters(pkg, O, simt, monkeypatch):
@@ -265,9 +264,8 @@ def test_group_check_catches_dirty_counters(pkg, O, simt, monkeypatch):
         w = (C.c_uint32 * COUNTERS)(*words)
         simt.simt_memset_fault(4 * COUNTERS, w, COUNTERS)
 
-    # (the one chunk is slot 0's)
     shifted = [0] * COUNTERS
-    shifted[1 * GROUP_SLOTS], shifted[2 * GROUP_SLOTS] = 0xFFFFFFFF, 1
+    shifted[1], shifted[2] = 0xFFFFFFFF, 1
     over = [0] * COUNTERS
     over[0] = 5
     for check, words, caught in (("1", shifted, True), ("0", shifted, False), ("0", over, True),
