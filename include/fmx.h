@@ -310,6 +310,48 @@ fmx_status fmx_locate_jobs_async(fmx_index *ix, const fmx_locate_job *jobs, uint
  * fmx_locate_batch_async on each job. */
 fmx_status fmx_locate_group_async(fmx_index *ix, const fmx_locate_job *jobs, uint64_t n_jobs, void *stream);
 
+/* ------------------------------------------------- longest-suffix match
+ * Greedy backward seeding, what a read mapper asks of a batched FM-index (no
+ * reference counterpart: FmIndex::count / locate answer only whether a whole
+ * pattern occurs).  Added within ABI 8: the additions are backward
+ * compatible, FMX_ABI_VERSION is unchanged.
+ * With pattern i in logical order p[0..m) (FMX_PATTERN_REVERSED as for locate:
+ * the bytes arrive last symbol first) and c = idx_of(byte):
+ *  - lens[i] = the largest L <= m for which the last L symbols S = p[m-L..m)
+ *    occur in the encoded text; 0 if the last symbol does not (or m = 0);
+ *  - ranges[2i], ranges[2i+1] = (lo, hi), P-wide: the interval of S in the
+ *    reduced row coordinates of get_pos_range (locate/with_slice.rs:21-33), so
+ *    hi - lo is the count of S; (0, 0) when L = 0;
+ *  - pattern i REPORTS when L >= max(min_len, 1) and hi - lo <= max_occ.  lens
+ *    and ranges are the true values either way; locations are emitted for
+ *    reporting patterns only: loc_offsets[i+1] - loc_offsets[i] is hi - lo for
+ *    them and 0 for the rest, in suffix-array-row order — what
+ *    fmx_locate_batch returns for S.
+ * Nothing here is an error of its own: an empty pattern gives L = 0, and a
+ * PassThrough byte >= symbol_count ends the match before it, like any symbol
+ * that does not extend the interval (a disagreeing FMX_HINT_FIXED_LEN is still
+ * FMX_E_ARG).  The search reads the blob's own k-mer table (the seed; suffixes
+ * shorter than k through its m < k form, count_array.rs:203-223) and the
+ * index's occ records in whichever encoding it was loaded with; derived
+ * structures do not shorten it (a loaded full SA serves the locations).
+ * out_loc_offsets == NULL (d_loc_offsets == NULL) selects lengths and
+ * intervals only: the location arguments and the workspace are ignored.
+ * Otherwise the capacity contract is fmx_locate_batch's (*needed written,
+ * FMX_E_CAPACITY if it exceeds cap; lens, ranges and offsets are written
+ * either way), and the device call's workspace has the size of
+ * fmx_locate_workspace_size and the same 16-B alignment rule.  The host call
+ * sets the staging and fixed-length hints itself.  A match runs in launch
+ * order: k_match, then the locate's k_emit.  Timer: "match". */
+fmx_status fmx_match_batch(fmx_index *ix, const uint8_t *bytes, const uint64_t *offsets,
+                           uint64_t n_patterns, uint32_t flags, uint32_t min_len, uint64_t max_occ,
+                           uint32_t *out_lens, void *out_ranges, uint64_t *out_loc_offsets,
+                           void *out_locs, uint64_t cap, uint64_t *needed);
+fmx_status fmx_match_batch_async(fmx_index *ix, const uint8_t *d_bytes, const uint64_t *d_offsets,
+                                 uint64_t n_patterns, uint32_t flags, uint32_t min_len, uint64_t max_occ,
+                                 uint32_t *d_lens, void *d_ranges, uint64_t *d_loc_offsets, void *d_locs,
+                                 uint64_t cap, uint64_t *d_needed, void *d_workspace,
+                                 uint64_t workspace_bytes, void *stream);
+
 /* Wait for `stream` and return (and clear) the latched device status. */
 fmx_status fmx_sync(fmx_index *ix, void *stream);
 
@@ -356,8 +398,9 @@ fmx_status fmx_multi_locate_batch(fmx_multi *m, const uint8_t *bytes, const uint
  * durations per kernel since timing was last enabled (enabling resets the
  * totals; fmx_timing_read synchronises).  An event pair costs the stream
  * several microseconds, so throughput runs sample (k > 1).  Timers: "count",
- * "locate" (a whole locate launch) and, for fmx_locate_group_async, its two
- * kernels "locate.search" (k_search) and "locate.emit" (k_emit). */
+ * "locate" (a whole locate launch), "match" (a whole match launch) and, for
+ * fmx_locate_group_async, its two kernels "locate.search" (k_search) and
+ * "locate.emit" (k_emit). */
 fmx_status fmx_timing_enable(fmx_index *ix, int enable);
 fmx_status fmx_timing_read(fmx_index *ix, fmx_kernel_timing *out, int max_entries, int *n_entries);
 

@@ -14,7 +14,9 @@ this module                    reference (sview-fmindex/src/...)
 ``FmIndex.blob``               ``FmIndex::blob``                 reference_to_source_blob.rs:9-11
 ``FmIndex.count_batch`` /      (new) one kernel launch for a whole pattern batch
 ``FmIndex.locate_batch``
-``FmIndexBuilder``             ``FmIndexBuilder``                builder/mod.rs:59-264 (built on the GPU)
+``FmIndex.match`` /            (new) longest-suffix match: greedy backward seeding
+``FmIndex.match_batch``
+``FmIndexBuilder``            ``FmIndexBuilder``                builder/mod.rs:59-264 (built on the GPU)
 ``blocks.Block2..Block6``      ``blocks::Block2..Block6<V>``     components/bwm/blocks/
 ``text_encoders.*``            ``EncodingTable`` / ``PassThrough`` components/text_encoder/
 ``build_config.*``             ``LookupTableConfig`` / ``SuffixArrayConfig`` builder/build_config/
@@ -543,6 +545,48 @@ class FmIndex:
         _check(st, "fmx_locate_batch")
         return loc_off, locs[:needed.value]
 
+    # -- longest-suffix match (greedy backward seeding) ---------------------
+    def match(self, pattern: bytes) -> Tuple[int, int, int]:
+        """(length, lo, hi): the longest suffix of `pattern` that occurs in the
+        text and its suffix-array interval (hi - lo occurrences; (0, 0, 0)
+        when not even the last symbol occurs)."""
+        lens, rng = self.match_batch([pattern], locate=False)
+        return int(lens[0]), int(rng[0, 0]), int(rng[0, 1])
+
+    def match_batch(self, patterns, reversed: bool = False, locate: bool = True, min_len: int = 1,
+                    max_occ: Optional[int] = None):
+        """Longest-suffix match of many patterns (fmx_match_batch): (lens
+        uint32[n], ranges P[n, 2]) and, with `locate`, (..., loc_offsets
+        uint64[n+1], locations P[total]).  lens[i] is the length of the longest
+        suffix of pattern i that occurs in the text and ranges[i] = (lo, hi) its
+        interval, always the true values; locations (suffix-array-row order)
+        are emitted only for patterns with lens[i] >= max(min_len, 1) and
+        hi - lo <= max_occ (None: no bound)."""
+        data, offsets = patterns if isinstance(patterns, tuple) else pack_patterns(patterns)
+        n = offsets.size - 1
+        lens = np.zeros(max(n, 1), dtype=np.uint32)
+        rng = np.zeros((max(n, 1), 2), dtype=self._dt)
+        flags = _n.FMX_PATTERN_REVERSED if reversed else 0
+        occ = (1 << 64) - 1 if max_occ is None else int(max_occ)
+        needed = C.c_uint64()
+        if not locate:
+            _check(_n.lib().fmx_match_batch(self._h, _ptr(data) if data.size else None, _ptr(offsets), n, flags,
+                                            int(min_len), occ, _ptr(lens), _ptr(rng), None, None, 0,
+                                            C.byref(needed)), "fmx_match_batch")
+            return lens[:n], rng[:n]
+        loc_off = np.zeros(n + 1, dtype=np.uint64)
+        cap = 1 << 16
+        locs = np.zeros(cap, dtype=self._dt)
+        args = lambda: (self._h, _ptr(data) if data.size else None, _ptr(offsets), n, flags, int(min_len), occ,  # noqa
+                        _ptr(lens), _ptr(rng), _ptr(loc_off), _ptr(locs), cap, C.byref(needed))
+        st = _n.lib().fmx_match_batch(*args())
+        if st == _n.FMX_E_CAPACITY:
+            cap = needed.value
+            locs = np.zeros(max(cap, 1), dtype=self._dt)
+            st = _n.lib().fmx_match_batch(*args())
+        _check(st, "fmx_match_batch")
+        return lens[:n], rng[:n], loc_off, locs[:needed.value]
+
     # -- device-resident API (pointers are ints; stream is a hipStream_t) --
     def count_batch_async(self, d_bytes: int, d_offsets: int, n: int, d_counts: int,
                           stream: int = 0, reversed: bool = False, long_patterns: bool = False, stage_kb: int = 0,
@@ -568,6 +612,23 @@ class FmIndex:
             C.c_void_p(d_counts) if d_counts else None, C.c_void_p(d_loc_offsets), C.c_void_p(d_locs), cap,
             C.c_void_p(d_needed) if d_needed else None, C.c_void_p(d_ws), ws_bytes,
             C.c_void_p(stream) if stream else None))
+
+    def match_batch_async(self, d_bytes: int, d_offsets: int, n: int, d_lens: int, d_ranges: int,
+                          d_loc_offsets: int = 0, d_locs: int = 0, cap: int = 0, d_needed: int = 0, d_ws: int = 0,
+                          ws_bytes: int = 0, min_len: int = 1, max_occ: Optional[int] = None, stream: int = 0,
+                          reversed: bool = False, long_patterns: bool = False, stage_kb: int = 0,
+                          fixed_len: int = 0) -> None:
+        """fmx_match_batch_async: d_lens uint32[n], d_ranges P[2 n]; with
+        d_loc_offsets (uint64[n+1]) also the locations of the reporting
+        patterns, into d_locs (cap entries) with the total in d_needed, over a
+        workspace of locate_workspace_size(n) bytes; d_loc_offsets = 0:
+        lengths and intervals only, no workspace."""
+        flags = _flags(reversed, long_patterns, stage_kb, fixed_len)
+        v = lambda x: C.c_void_p(x) if x else None  # noqa: E731
+        _check(_n.lib().fmx_match_batch_async(
+            self._h, C.c_void_p(d_bytes), C.c_void_p(d_offsets), n, flags, int(min_len),
+            (1 << 64) - 1 if max_occ is None else int(max_occ), C.c_void_p(d_lens), C.c_void_p(d_ranges),
+            v(d_loc_offsets), v(d_locs), cap, v(d_needed), v(d_ws), ws_bytes, v(stream)))
 
     @staticmethod
     def locate_job(d_bytes: int, d_offsets: int, n: int, d_loc_offsets: int, d_locs: int, cap: int,

@@ -1215,6 +1215,35 @@ fmx_status fmx_locate_batch_async(fmx_index *ix, const uint8_t *d_bytes, const u
     });
 }
 
+fmx_status fmx_match_batch_async(fmx_index *ix, const uint8_t *d_bytes, const uint64_t *d_offsets, uint64_t n,
+                                 uint32_t flags, uint32_t min_len, uint64_t max_occ, uint32_t *d_lens, void *d_ranges,
+                                 uint64_t *d_loc_offsets, void *d_locs, uint64_t cap, uint64_t *d_needed, void *d_ws,
+                                 uint64_t ws_bytes, void *stream) {
+    if (!ix || (n && (!d_bytes || !d_offsets || !d_lens || !d_ranges))) return FMX_E_ARG;
+    const bool loc = d_loc_offsets != nullptr;  // (else: lengths and intervals only, no workspace)
+    if (loc) {
+        if (!d_needed || (cap && !d_locs)) return FMX_E_ARG;
+        if (!d_ws || ws_bytes < kWsHeader + 16 || ((uintptr_t)d_ws & 15) != 0) return FMX_E_ARG;
+        if (n && ws_bytes < ws_bytes_for(ix, n)) return FMX_E_ARG;
+    }
+    hipStream_t s = stream ? (hipStream_t)stream : ix->stream;
+    DeviceGuard dg(ix->device);
+    if (n == 0) {
+        if (!loc) return FMX_OK;
+        hipError_t e = hipMemsetAsync(d_loc_offsets, 0, 8, s);
+        if (e == hipSuccess) e = hipMemsetAsync(d_needed, 0, 8, s);
+        return dev_err(e);
+    }
+    uint8_t *ws = (uint8_t *)d_ws;
+    const uint64_t G = locate_tiles_cap(n);
+    return with_status(ix, s, [&](uint32_t *status) {
+        return dev_err(timed(ix, "match", s, n, [&] {
+            return launch_match(ix, d_bytes, d_offsets, n, flags, min_len, max_occ, d_lens, d_ranges, d_loc_offsets,
+                                d_locs, cap, d_needed, loc ? (uint64_t *)(ws + kWsHeader) : nullptr, G, status, s);
+        }));
+    });
+}
+
 fmx_status fmx_locate_jobs_async(fmx_index *ix, const fmx_locate_job *jobs, uint64_t n_jobs) {
     if (!ix || (n_jobs && !jobs)) return FMX_E_ARG;
     for (uint64_t i = 0; i < n_jobs; ++i) {
@@ -1430,6 +1459,71 @@ fmx_status fmx_locate_batch(fmx_index *ix, const uint8_t *bytes, const uint64_t 
             return dev_err(e);
         }
         dcap = total;  // second pass with room for every location
+    }
+    return FMX_E_DEVICE;
+}
+
+// Longest-suffix match of a host batch: as fmx_locate_batch (same scratch,
+// workspace, capacity contract and output-size retry), plus the lengths and
+// intervals.  An empty pattern is no error here (its length is 0).
+fmx_status fmx_match_batch(fmx_index *ix, const uint8_t *bytes, const uint64_t *offsets, uint64_t n, uint32_t flags,
+                           uint32_t min_len, uint64_t max_occ, uint32_t *out_lens, void *out_ranges,
+                           uint64_t *out_loc_offsets, void *out_locs, uint64_t cap, uint64_t *needed) {
+    const bool loc = out_loc_offsets != nullptr;
+    if (!ix || (n && (!offsets || !out_lens || !out_ranges)) || (loc && cap && !out_locs)) return FMX_E_ARG;
+    if (needed) *needed = 0;
+    if (n == 0) {
+        if (loc) out_loc_offsets[0] = 0;
+        return FMX_OK;
+    }
+    if (offsets[0] != 0) return FMX_E_ARG;
+    for (uint64_t i = 0; i < n; ++i)
+        if (offsets[i + 1] < offsets[i]) return FMX_E_ARG;
+    if (offsets[n] && !bytes) return FMX_E_ARG;
+    std::lock_guard<std::mutex> g(ix->mu);
+    DeviceGuard dg(ix->device);
+    const uint64_t nb = offsets[n], pb = ix->bv.L.pos_bytes;
+    flags = (flags & 0xffu) | stage_hint(offsets, n);
+    fmx_status st = loc ? ensure_ws(ix, n) : FMX_OK;
+    if (st) return st;
+    const uint64_t o_off = align_up(std::max<uint64_t>(nb, 1), 256);
+    const uint64_t o_len = o_off + align_up((n + 1) * 8, 256);
+    const uint64_t o_rng = o_len + align_up(n * 4, 256);
+    const uint64_t o_loff = o_rng + align_up(2 * n * pb, 256);
+    const uint64_t o_need = o_loff + align_up((n + 1) * 8, 256);
+    const uint64_t o_locs = o_need + 256;
+    hipStream_t s = ix->stream;
+    // the output size guessed as fmx_locate_batch does; a second pass if it was short
+    uint64_t dcap = loc ? std::min<uint64_t>(cap, std::max<uint64_t>(n, ix->scratch_bytes > o_locs
+                                                                             ? (ix->scratch_bytes - o_locs) / pb : 0))
+                        : 0;
+    for (int pass = 0; pass < 2; ++pass) {
+        st = ensure_scratch(ix, loc ? o_locs + std::max<uint64_t>(dcap, 1) * pb : o_loff);
+        if (st) return st;
+        uint8_t *d = ix->d_scratch;
+        hipError_t e = ix->stage.h2d(d, bytes, nb, s);
+        if (e == hipSuccess) e = ix->stage.h2d(d + o_off, offsets, (n + 1) * 8, s);
+        if (e != hipSuccess) return FMX_E_DEVICE;
+        st = fmx_match_batch_async(ix, d, (uint64_t *)(d + o_off), n, flags, min_len, max_occ, (uint32_t *)(d + o_len),
+                                   d + o_rng, loc ? (uint64_t *)(d + o_loff) : nullptr, d + o_locs, dcap,
+                                   (uint64_t *)(d + o_need), ix->d_ws, ix->ws_bytes, s);
+        if (st) return st;
+        uint64_t total = 0;
+        if (loc && ix->stage.d2h(&total, d + o_need, 8, s) != hipSuccess) return FMX_E_DEVICE;
+        st = read_status(ix, s);
+        if (st) return st;
+        if (needed) *needed = total;
+        if (total > dcap && total <= cap) {
+            dcap = total;  // second pass with room for every location
+            continue;
+        }
+        e = ix->stage.d2h(out_lens, d + o_len, n * 4, s);
+        if (e == hipSuccess) e = ix->stage.d2h(out_ranges, d + o_rng, 2 * n * pb, s);
+        if (e == hipSuccess && loc) e = ix->stage.d2h(out_loc_offsets, d + o_loff, (n + 1) * 8, s);
+        if (e != hipSuccess) return FMX_E_DEVICE;
+        if (total > cap) return FMX_E_CAPACITY;
+        if (total) e = ix->stage.d2h(out_locs, d + o_locs, total * pb, s);
+        return dev_err(e);
     }
     return FMX_E_DEVICE;
 }

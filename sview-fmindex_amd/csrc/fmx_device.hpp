@@ -1028,6 +1028,95 @@ FMX_HD uint32_t search_seeded(const QueryArgs &a, const Tables<P> &s, const PatV
     return 0;
 }
 
+// Longest-suffix match (greedy backward seeding): the largest L <= m for which
+// the pattern's last L symbols S = P[m-L..m) occur in the text, and S's
+// interval [lo, hi) in the reduced row coordinates of get_pos_range (L = 0:
+// lo = hi = 0).  Never an error: an empty pattern gives L = 0, and a symbol
+// >= sigma (PassThrough) ends the match before it like any symbol that does
+// not extend the interval.  The blob's own k-mer table and the occ records
+// only: derived structures do not shorten it.
+// Seed: the last t = min(m, k) symbols in the table's m < k form
+// (count_array.rs:203-223: the codes [s, s + mult[t-1] - 1] are the k-mers
+// that start with them, the text's end padded with sentinels), retried with
+// t - 1 while that interval is empty — dropping the first of the t symbols
+// turns s into (s - (c + 1) mult[0]) (sigma + 1), since mult[j] = (sigma +
+// 1)^(k-1-j).  A hit below min(m, k) symbols, or of the whole pattern, is
+// final; else the LF loop of search_seeded goes on from m - k, each step's
+// interval computed first and committed only if it is not empty — so that
+// SampledRow sees committed intervals only (a step rolled back that had still
+// bumped `off` would put the location one too low).
+template <typename P, int N, int VB, int REC>
+FMX_HD void match_suffix(const QueryArgs &a, const Tables<P> &s, const PatView &pv, P &lo, P &hi, uint32_t &len,
+                         SampledRow<P> &smp, bool locate) {
+    using O = Occ<P, N, VB, REC>;
+    smp.valid = 0;
+    const uint32_t sigma = a.sigma, k = a.k;
+    const uint64_t m = pv.m;
+    const P sent = (P)a.sentinel;
+    lo = hi = 0;
+    len = 0;
+    // the seed's symbols: the pattern's last ones below sigma, at most min(m, k)
+    const uint32_t top = (uint32_t)(m < k ? m : k);
+    uint32_t t = 0;
+    while (t < top && pv.at(m - 1 - t) < sigma) ++t;
+    const bool whole = t == top;  // (no symbol >= sigma among the last min(m, k))
+    uint64_t code = 0;
+    for (uint32_t j = 0; j < t; ++j) code += (uint64_t)(pv.at(m - t + j) + 1) * s.mult[j];
+    const uint64_t W = (uint64_t)sigma + 1;
+    for (; t > 0; --t) {
+        lo = s.kt[code - 1];
+        hi = s.kt[code + s.mult[t - 1] - 1];
+        if (lo < hi) break;
+        code = (code - (uint64_t)(pv.at(m - t) + 1) * s.mult[0]) * W;
+    }
+    if (t == 0) {
+        lo = hi = 0;
+        return;
+    }
+    uint64_t idx = m - t;
+    // (only when the caller locates; a by-reference smp stays in registers, an optional pointer would not)
+    const bool track = FMX_SAMPLED_ROW && locate && a.safull == nullptr;
+    uint64_t sslot = 0;
+    P soff = 0;
+    bool shave = false;
+    auto note = [&]() {  // (after every committed interval, as search_seeded's)
+        if (shave) soff += P(1);
+        if (hi - lo == P(1)) {
+            uint64_t rem;
+            const uint64_t sl = sr_div(a, (uint64_t)lo, rem);
+            if (rem == 0) {
+                sslot = sl;
+                soff = 0;
+                shave = true;
+            }
+        }
+    };
+    if (track) note();
+    if (whole && t == top) {
+        // LF loop: with_slice.rs:27-31, next_pos_range (locate/mod.rs:39-45)
+        uint32_t c = idx > 0 ? pv.at(idx - 1) : 0;  // next symbol, fetched one step ahead
+        while (idx > 0 && c < sigma) {
+            const P plo = lo + (lo < sent ? P(1) : P(0));  // bwm/mod.rs:202-204
+            const P phi = hi + (hi < sent ? P(1) : P(0));
+            P rlo, rhi;
+            O::rank_pair(a, plo, phi, c, rlo, rhi);
+            const P pre = s.C[c];
+            if (!(rlo < rhi)) break;  // the longer suffix does not occur: keep the last interval
+            idx -= 1;
+            c = idx > 0 ? pv.at(idx - 1) : 0;
+            lo = pre + rlo;
+            hi = pre + rhi;
+            if (track) note();
+        }
+    }
+    len = (uint32_t)(m - idx);
+    if (track && shave && hi - lo == P(1)) {
+        smp.slot = sslot;
+        smp.off = soff;
+        smp.valid = 1;
+    }
+}
+
 // A value read once by one lane (the sampled-SA entry of a walk): a
 // non-temporal load on the device, so that its line does not displace the
 // occ records that other patterns read again.

@@ -350,6 +350,28 @@ inline void group_reset(LocateGroup &g) {
     g.gn = g.vbase = 0;
     g.tickets = nullptr;
 }
+// One longest-suffix match batch (k_match; fmx_match_batch_async): every
+// pattern's matched length and interval; with recs (the locate workspace's
+// search records, after its 2 G tile words at `tiles`) also the record and
+// the tile counts that k_scan / k_emit turn into offsets and locations.
+struct MatchBatch {
+    const uint8_t *bytes;
+    const uint64_t *offs;
+    uint64_t npat;
+    uint32_t *out_len;
+    void *out_rng;    // 2 P-wide words per pattern: lo, hi
+    uint64_t *tiles;  // null: lengths and intervals only
+    uint64_t max_occ;
+    uint32_t min_len;
+    uint32_t rev;
+    uint32_t stride;  // FMX_HINT_FIXED_LEN (0: read the offsets)
+};
+// k_match, then (d_loc_offsets non-null) k_scan / k_emit over the records it
+// left: d_tiles as for launch_locate.  In launch order only.
+hipError_t launch_match(const fmx_index *ix, const uint8_t *d_bytes, const uint64_t *d_offsets, uint64_t n,
+                        uint32_t flags, uint32_t min_len, uint64_t max_occ, uint32_t *d_lens, void *d_ranges,
+                        uint64_t *d_loc_offsets, void *d_locs, uint64_t cap, uint64_t *d_needed, uint64_t *d_tiles,
+                        uint64_t tiles_cap, uint32_t *status, hipStream_t stream);
 // `mid` (optional): an event recorded between k_search and k_emit (timing).
 // Fills grp's per-launch fields (first, emit_begin, the grouped fields) in place.
 hipError_t launch_locate_group(const fmx_index *ix, LocateGroup &grp, uint32_t stage_flags,
@@ -477,6 +499,9 @@ struct LayoutOps {
     // a grouped launch's last kernel with the tile counts handed from tile to tile (k_emit_chain)
     hipError_t (*emit_chain)(const QueryArgs &qa, uint32_t vb, uint32_t rec, const LocateGroup &grp, uint32_t tiles,
                              uint64_t tag, uint64_t late_ticks, hipStream_t s);
+    // longest-suffix match (k_match): every record encoding, no search variant
+    hipError_t (*match)(const QueryArgs &qa, uint32_t vb, uint32_t rec, const MatchBatch &mb, uint32_t tiles,
+                        uint32_t sb, hipStream_t s);
 };
 uint64_t locate_tiles_cap(uint64_t n);
 // Bytes per pattern of the search-result records in the locate workspace.

@@ -1,5 +1,5 @@
 // fmx_kernels.hpp — the query kernels that depend on the occ layout (P, N,
-// V, record size): k_count, k_search, k_emit, the deep-table level step, the
+// V, record size): k_count, k_search, k_match, k_emit, the deep-table level step, the
 // full-SA walk and the record re-layout.  Instantiated per (P, N) in its own
 // translation unit (fmx_layout.hip, one object per layout, built in
 // parallel); launched through the LayoutOps table (fmx_internal.hpp).
@@ -371,6 +371,57 @@ __global__ __launch_bounds__(256, VAR == kVarDerivedLong ? 4 : 8) void k_search(
     __shared__ uint64_t s_scan[4];
     stage_tables(a, s, s_pat + stage_bytes);
     search_tile<P, N, VB, REC, VAR>(a, grp, s, s_pat, s_scan, stage_bytes, blockIdx.x);
+}
+
+// ------------------------------------------------ k_match (longest suffix)
+// One lane per pattern, as k_search: the length of the longest suffix of the
+// pattern that occurs in the text and its interval (match_suffix), always
+// written.  With B.tiles (locations asked for) the lane also leaves the search
+// record k_emit reads — {lo, count, 0}, the count 0 unless the pattern reports
+// (length >= max(min_len, 1) and count <= max_occ); one row located here,
+// while the lane's chain is live, as search_lane does — and the workgroup its
+// tile's count, so that k_scan / k_emit write the offsets, the total and the
+// locations exactly as for a locate.
+template <typename P, int N, int VB, int REC>
+__global__ __launch_bounds__(256, 8) void k_match(const QueryArgs a, const MatchBatch B, uint32_t stage_bytes) {
+    __shared__ Tables<P> s;
+    FMX_DYN_LDS(s_pat);  // stage_bytes, then the k-mer table (dynamic)
+    __shared__ uint64_t s_scan[4];
+    stage_tables(a, s, s_pat + stage_bytes);
+    const uint8_t *__restrict__ bytes = B.bytes;
+    const uint64_t npat = B.npat, first = (uint64_t)blockIdx.x * 256u;
+    const bool rev = B.rev != 0;
+    uint64_t beg, end, b0, b1;
+    const bool staged =
+        stage_patterns(s, s_pat, bytes, B.offs, npat, first, rev, stage_bytes, B.stride, a.status, beg, end, b0, b1);
+    __syncthreads();
+    const uint64_t i = first + threadIdx.x;
+    const bool loc = B.tiles != nullptr;  // (workgroup-uniform)
+    uint64_t cnt = 0;
+    if (i < npat) {
+        const PatView pv = pattern_view(s, s_pat, staged, bytes, beg, end, b0, b1, rev);
+        P lo, hi;
+        uint32_t len;
+        SampledRow<P> smp;
+        match_suffix<P, N, VB, REC>(a, s, pv, lo, hi, len, smp, loc);
+        B.out_len[i] = len;
+        P *__restrict__ rng = reinterpret_cast<P *>(B.out_rng) + 2 * i;
+        rng[0] = lo;
+        rng[1] = hi;
+        if (loc) {
+            const uint64_t G = (npat + 255) / 256;
+            SearchRec<P> *__restrict__ recs = reinterpret_cast<SearchRec<P> *>(B.tiles + 2 * G);
+            const uint32_t need = B.min_len > 1u ? B.min_len : 1u;
+            if (len >= need && (uint64_t)(hi - lo) <= B.max_occ) cnt = (uint64_t)(hi - lo);
+            if (cnt == 1) recs[i] = SearchRec<P>{locate_one<P, N, VB, REC>(a, s.C, lo, smp), P(1), 1ull};
+            else recs[i] = SearchRec<P>{lo, (P)cnt, 0ull};
+        }
+    }
+    if (loc) {
+        uint64_t agg;
+        block_excl_scan(cnt, &agg, s_scan);
+        if (threadIdx.x == 0) B.tiles[blockIdx.x] = agg;
+    }
 }
 
 // ------------------------------------------- k_locate (search + emit, fused)

@@ -179,6 +179,14 @@ hipError_t disp(uint32_t vb, uint32_t rec, F &&f) {
     });
 }
 
+[[maybe_unused]] hipError_t op_match(const QueryArgs &qa, uint32_t vb, uint32_t rec, const MatchBatch &mb, uint32_t tiles,
+                                     uint32_t sb, hipStream_t s) {
+    return disp(vb, rec, [&]<int VB, int R>() {
+        hipLaunchKernelGGL((k_match<P, N, VB, R>), dim3(tiles), dim3(256), sb + qa.kt_lds_bytes, s, qa, mb, sb);
+        return hipGetLastError();
+    });
+}
+
 }  // namespace
 
 #if !defined(__HIP_DEVICE_COMPILE__)  // a host table (the device pass only instantiates the kernels)
@@ -187,7 +195,7 @@ hipError_t disp(uint32_t vb, uint32_t rec, F &&f) {
 extern const LayoutOps FMX_OPS_NAME(FMX_LAYOUT_P, FMX_LAYOUT_N, FMX_LAYOUT_VB);
 const LayoutOps FMX_OPS_NAME(FMX_LAYOUT_P, FMX_LAYOUT_N, FMX_LAYOUT_VB) = {op_count, op_search, op_emit, op_search_grouped,
                                                            op_dlut_level, op_full_sa, op_relayout, op_locate,
-                                                           op_emit_chain};
+                                                           op_emit_chain, op_match};
 #endif
 
 }  // namespace fmx

@@ -11,6 +11,10 @@
 //                get_pre_rank_and_symidx, components/bwm/mod.rs:217-236;
 //                SuffixArrayView::get_location_of, suffix_array/mod.rs:100-105)
 //               and leaves a search record per pattern plus its tile's count
+//   k_match   : the longest suffix of each pattern that occurs in the text
+//               (greedy backward seeding; no reference counterpart): the seed
+//               steps down to shorter suffixes, LF steps are committed only
+//               while the interval stays non-empty; then k_scan / k_emit
 //   k_scan    : tile offsets of batches too large for k_emit's own sum
 //   k_emit    : output offsets, then every location: settled ones copied,
 //               the rows of multi-row intervals walked, dealt across the 64
@@ -678,6 +682,32 @@ hipError_t launch_locate(const fmx_index *ix, const uint8_t *d_bytes, const uint
                            (flags & FMX_PATTERN_REVERSED) ? 1u : 0u, flags >> 16};
     grp.n = 1;
     return launch_split(ix, qa, grp, (uint32_t)((n + 255) / 256), stage_bytes_for(flags), stream);
+}
+
+// Longest-suffix match, in launch order: k_match, then — when locations are
+// asked for — the locate's own last kernels over the records it left.
+hipError_t launch_match(const fmx_index *ix, const uint8_t *d_bytes, const uint64_t *d_offsets, uint64_t n,
+                        uint32_t flags, uint32_t min_len, uint64_t max_occ, uint32_t *d_lens, void *d_ranges,
+                        uint64_t *d_loc_offsets, void *d_locs, uint64_t cap, uint64_t *d_needed, uint64_t *d_tiles,
+                        uint64_t tiles_cap, uint32_t *status, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    QueryArgs qa = ix->qa;
+    qa.status = status;
+    const uint64_t tiles = (n + 255) / 256;
+    const bool loc = d_loc_offsets != nullptr;
+    if (tiles > 0x7FFFFFFFull || (loc && (tiles > tiles_cap || !d_tiles))) return hipErrorInvalidValue;
+    const uint32_t rev = (flags & FMX_PATTERN_REVERSED) ? 1u : 0u, stride = flags >> 16;
+    const MatchBatch mb{d_bytes, d_offsets, n, d_lens, d_ranges, loc ? d_tiles : nullptr, max_occ, min_len, rev, stride};
+    const Disp d = dispatch(ix);
+    hipError_t e = d.ops->match(qa, d.vb, d.rec, mb, (uint32_t)tiles, stage_bytes_for(flags), stream);
+    if (e != hipSuccess || !loc) return e;
+    // one batch in launch order for k_scan / k_emit (neither reads the patterns)
+    LocateGroup grp;
+    group_reset(grp);
+    grp.tile_begin[0] = 0;
+    grp.b[0] = LocateBatch{d_bytes, d_offsets, n, nullptr, d_loc_offsets, d_locs, cap, d_needed, d_tiles, rev, stride};
+    grp.n = 1;
+    return launch_emit(ix, qa, grp, (uint32_t)tiles, 0u, stream);
 }
 
 static hipError_t check_group(const LocateGroup &grp, uint64_t *tiles) {

@@ -1,0 +1,180 @@
+"""Longest-suffix match (fmx_match_batch): the cases and expected values the
+emulator tests (test_match_simt.py) and the GPU tests (test_gpu_match.py)
+share.
+
+Expected values, per pattern p of length m (computed once per text and
+cached):
+  * L = the largest t with OracleIndex.count(p[m-t:]) > 0 (monotone in t: a
+    suffix of an occurring string occurs), 0 if none;
+  * S = p[m-L:]; hi - lo = OracleIndex.count(S); the locations are
+    OracleIndex.locate(S), element-wise;
+  * lo = the number of non-empty suffixes of the encoded text that sort before
+    S by plain byte order (a proper prefix first), from a suffix list sorted
+    in Python — and OracleIndex.locate(S) must equal sa[lo:hi] of that list,
+    which ties the oracle's row order to the plain order (asserted here, on
+    the reference alone, before anything is compared with it).
+"""
+import bisect
+
+import numpy as np
+
+from _util import encode, rand_chr_list, rand_text, table_from_symbols
+
+ABSENT = 0  # byte 0x00: maps to the wildcard symbol, which no text here holds
+BATCH_SIZES = (1, 255, 256, 257, 700)
+
+
+class Case:
+    """One text: `nchars` distinct printable bytes plus a wildcard symbol that
+    does not occur in it (symbol_count = nchars + 1), k and sr in 1..4."""
+
+    def __init__(self, seed, nchars, k=None, sr=None):
+        rng = np.random.default_rng(seed)
+        self.chars = rand_chr_list(rng, nchars)
+        self.table = table_from_symbols([bytes([c]) for c in self.chars], with_wildcard=True)
+        self.sigma = nchars + 1
+        self.text = rand_text(rng, self.chars, 300, 4000)
+        self.k = int(rng.integers(1, 5)) if k is None else k
+        self.sr = int(rng.integers(1, 5)) if sr is None else sr
+        while (self.sigma + 1) ** self.k > 1 << 20:
+            self.k -= 1
+        self.seed = seed
+        self.enc = encode(self.table, self.text)
+        self._sa = None
+        self._exp = {}
+
+    def blob(self, O, pb, planes, vb):
+        return O.build(self.text, self.sigma, O.layout(pb, planes, vb), self.k, self.sr, self.table)
+
+    # -- the reference ---------------------------------------------------
+    def suffixes(self):
+        if self._sa is None:
+            e = self.enc
+            sa = sorted(range(len(e)), key=lambda i: e[i:])
+            self._sa = (sa, [e[i:] for i in sa])
+        return self._sa
+
+    def expected(self, orc, p):
+        """(L, lo, hi, locations) of pattern p (bytes, logical order)."""
+        got = self._exp.get(p)
+        if got is not None:
+            return got
+        m = len(p)
+        lo_t, hi_t = 0, m  # count(p[m-t:]) > 0 for t <= lo_t; binary search on the monotone predicate
+        while lo_t < hi_t:
+            mid = (lo_t + hi_t + 1) // 2
+            if orc.count(p[m - mid:]) > 0:
+                lo_t = mid
+            else:
+                hi_t = mid - 1
+        L = lo_t
+        if L == 0:
+            got = (0, 0, 0, [])
+        else:
+            S = p[m - L:]
+            cnt = orc.count(S)
+            locs = orc.locate(S)
+            sa, suf = self.suffixes()
+            lo = bisect.bisect_left(suf, encode(self.table, S))
+            assert len(locs) == cnt and locs == sa[lo:lo + cnt], "oracle row order != plain suffix order"
+            assert L == m or orc.count(p[m - L - 1:]) == 0
+            got = (L, lo, lo + cnt, locs)
+        self._exp[p] = got
+        return got
+
+    # -- the patterns ------------------------------------------------------
+    def other(self, rng, c):
+        """A byte of the alphabet other than c (one symbol only: the absent byte)."""
+        rest = [x for x in self.chars if x != c]
+        return int(rng.choice(rest)) if rest else ABSENT
+
+    def core(self):
+        """Every case class once or more (fewer than 255 patterns)."""
+        rng = np.random.default_rng(self.seed + 1000)
+        t, k, n = self.text, self.k, len(self.text)
+        pats = []
+
+        def sub(m):
+            s = int(rng.integers(0, n - m))
+            return t[s:s + m]
+
+        def subst(p, j):
+            q = bytearray(p)
+            q[j] = self.other(rng, q[j])
+            return bytes(q)
+        # substrings: full matches
+        for m in sorted({1, 2, k - 1, k, k + 1, 7, 40} - {0}):
+            pats += [sub(m) for _ in range(4)]
+        # one symbol substituted: inside the last k (the seed falls back: L < k), at m - k - 1 (the first
+        # LF step fails: L = k), further left
+        for m in (k + 2, 12, 40):
+            for j in range(k):
+                pats.append(subst(sub(m), m - 1 - j))
+            pats += [subst(sub(m), m - k - 1) for _ in range(3)]
+            if m - k - 1 > 0:
+                pats += [subst(sub(m), int(rng.integers(0, m - k - 1))) for _ in range(3)]
+        # a last byte that the text does not hold: L = 0
+        pats += [sub(m) + bytes([ABSENT]) for m in (0, 1, k, 9)]
+        pats.insert(len(pats) // 2, b"")  # an empty pattern in mid-batch
+        # c + text[:j]: the match reaches the text start (the sentinel adjustment, the walk's text-start exit)
+        for c in list(self.chars) + [ABSENT]:
+            for j in (1, k, 9, 30):
+                pats.append(bytes([c]) + t[:j])
+        # substrings long enough to be unique, a wrong symbol before them: the match ends in the
+        # single-row phase with one step rolled back (the sampled-row bookkeeping)
+        for _ in range(12):
+            s = int(rng.integers(1, n - 30))
+            pats.append(bytes([self.other(rng, t[s - 1])]) + t[s:s + 30])
+        # an absent symbol in the middle and right before the seed
+        pats += [sub(6) + bytes([ABSENT]) + sub(k + 3), sub(3) + bytes([ABSENT]) + sub(k)]
+        assert len(pats) < 255
+        return pats
+
+    def batch(self, n):
+        """n patterns: one mismatching read for n = 1, else the core classes
+        followed by substrings, substituted or not."""
+        core = self.core()
+        if n == 1:
+            return [core[40]]
+        rng = np.random.default_rng(self.seed + n)
+        t, pats = self.text, list(core)
+        while len(pats) < n:
+            m = int(rng.integers(1, 41))
+            s = int(rng.integers(0, len(t) - m))
+            q = bytearray(t[s:s + m])
+            if rng.integers(0, 2):
+                j = int(rng.integers(0, m))
+                q[j] = self.other(rng, q[j])
+            pats.append(bytes(q))
+        return pats[:n]
+
+
+def check_match(pkg, ix, orc, case, pats, reversed=False, min_len=1, max_occ=None, locate=True):
+    """match_batch of `pats` against the expected values; returns them."""
+    exp = [case.expected(orc, p) for p in pats]
+    q = [p[::-1] for p in pats] if reversed else pats
+    out = ix.match_batch(q, reversed=reversed, locate=locate, min_len=min_len, max_occ=max_occ)
+    lens, rng = out[0], out[1]
+    n = len(pats)
+    assert lens.dtype == np.uint32 and lens.shape == (n,) and rng.shape == (n, 2)
+    eL = np.array([e[0] for e in exp], dtype=np.int64)
+    elo = np.array([e[1] for e in exp], dtype=np.int64)
+    ehi = np.array([e[2] for e in exp], dtype=np.int64)
+    bad = np.flatnonzero(lens.astype(np.int64) != eL)
+    assert bad.size == 0, (f"lengths differ for {bad.size} patterns, first {bad[:5].tolist()}: "
+                           f"{lens[bad[:5]].tolist()} expected {eL[bad[:5]].tolist()} ({[pats[i] for i in bad[:3]]})")
+    bad = np.flatnonzero((rng[:, 0].astype(np.int64) != elo) | (rng[:, 1].astype(np.int64) != ehi))
+    assert bad.size == 0, (f"ranges differ for {bad.size} patterns, first {bad[:5].tolist()}: "
+                           f"{rng[bad[:5]].tolist()} expected {list(zip(elo[bad[:5]].tolist(), ehi[bad[:5]].tolist()))}")
+    if not locate:
+        assert len(out) == 2
+        return exp
+    loff, locs = out[2], out[3]
+    need = max(min_len, 1)
+    rep = [e[0] >= need and (max_occ is None or e[2] - e[1] <= max_occ) for e in exp]
+    ecnt = np.array([e[2] - e[1] if r else 0 for e, r in zip(exp, rep)], dtype=np.uint64)
+    eoff = np.concatenate([np.zeros(1, np.uint64), np.cumsum(ecnt, dtype=np.uint64)])
+    assert np.array_equal(loff, eoff), "location offsets differ"
+    elocs = [x for e, r in zip(exp, rep) if r for x in e[3]]
+    assert np.array_equal(locs.astype(np.uint64), np.array(elocs, dtype=np.uint64)), "locations differ (SA-row order)"
+    return exp
