@@ -228,7 +228,25 @@ fmx_status fmx_locate_batch(fmx_index *ix, const uint8_t *bytes, const uint64_t 
  * read by fmx_sync().  Only `stream` orders the launch: the index's own
  * stream is non-blocking (not ordered with the caller's streams, nor with the
  * legacy default stream), so buffers written on another stream must be
- * complete first — pass the writers' stream, or synchronise. */
+ * complete first — pass the writers' stream, or synchronise.
+ *
+ * Alignment, sizes and padding of the device pointers (every call below):
+ *  - d_bytes needs no alignment and no padding past d_offsets[n_patterns].
+ *    The kernels read it in whole vectors aligned by ADDRESS (16 B; a grouped
+ *    launch's key pass 4 B), and only vectors that hold at least one byte of
+ *    the batch: up to 15 bytes before d_bytes and after its last byte are
+ *    read and ignored, never anything outside the aligned 16-B lines the
+ *    batch itself touches, so never another page.  Nothing is written to it.
+ *  - the uint64_t arrays (d_offsets, d_loc_offsets, d_needed): 8-B aligned;
+ *    d_lens: 4; the P-wide arrays (d_counts, d_locs, d_ranges): P.  Each is
+ *    accessed as elements of its own type only: exactly n_patterns + 1
+ *    offsets, n_patterns counts and lens, 2 n_patterns range words, one
+ *    needed word and at most cap locations — an array of exactly that size
+ *    is enough, and no byte outside it is read or written.
+ *  - the workspace: 16-B aligned, fmx_locate_workspace_size(n_patterns)
+ *    bytes; a launch may write any of it and nothing outside it.
+ *  - cap = 0 with d_locs = NULL sizes an output: the offsets, the counts and
+ *    *d_needed are written, no location is. */
 
 fmx_status fmx_count_batch_async(fmx_index *ix, const uint8_t *d_bytes, const uint64_t *d_offsets,
                                  uint64_t n_patterns, uint32_t flags, void *d_counts, void *stream);

@@ -111,12 +111,14 @@ __device__ __forceinline__ bool stage_patterns(const Tables<P> &s, uint8_t *s_pa
         return false;
     }
     using V4 = uint32_t __attribute__((ext_vector_type(4)));
-    const uint64_t a0 = b0 & ~15ull;
-    const uint32_t nv = (uint32_t)((b1 - a0 + 15) >> 4);
-    const V4 *src = reinterpret_cast<const V4 *>(bytes + a0);
+    // aligned by ADDRESS (d_bytes itself may have any alignment): the first
+    // vector holds the span's first byte, the last one its last byte
+    const uint64_t addr = reinterpret_cast<uint64_t>(bytes) + b0, a0 = addr & ~15ull;
     // 32-bit positions within the span (len <= stage_bytes): byte w of
     // vector v is span byte 16 v + w - lead, kept if below len (unsigned)
-    const uint32_t lead = (uint32_t)(b0 - a0), len32 = (uint32_t)len;
+    const uint32_t lead = (uint32_t)(addr - a0), len32 = (uint32_t)len;
+    const uint32_t nv = len32 ? (lead + len32 + 15) >> 4 : 0u;  // (an empty span: no vector holds a byte of it)
+    const V4 *src = reinterpret_cast<const V4 *>(a0);
     for (uint32_t v0 = 0; v0 < nv; v0 += 4 * 256) {
         V4 x[4];
 #pragma unroll
@@ -702,9 +704,10 @@ __global__ __launch_bounds__(1024, W <= 8 ? 2 : 1) void k_group_key(const QueryA
 #pragma unroll
     for (uint32_t g = 0; g < G; ++g) {
         const uint64_t i = first + (p0 + g) * T + t;
-        const uint64_t beg = i * m + skip, a0 = beg & ~3ull;
+        // aligned words by ADDRESS (the batch's bytes may have any alignment)
+        const uint64_t beg = reinterpret_cast<uint64_t>(B.bytes) + i * m + skip, a0 = beg & ~3ull;
         lead[g] = (uint32_t)(beg - a0);
-        const uint32_t *src = reinterpret_cast<const uint32_t *>(B.bytes + a0);
+        const uint32_t *src = reinterpret_cast<const uint32_t *>(a0);
         const bool ok = i < n;
 #pragma unroll
         for (uint32_t q = 0; q < W; ++q) x[g][q] = ok && 4 * q < lead[g] + span ? src[q] : 0u;
