@@ -243,8 +243,13 @@ fmx_status fmx_locate_batch(fmx_index *ix, const uint8_t *bytes, const uint64_t 
  *    offsets, n_patterns counts and lens, 2 n_patterns range words, one
  *    needed word and at most cap locations — an array of exactly that size
  *    is enough, and no byte outside it is read or written.
+ *    fmx_seeds_batch_async, with S = n_patterns * max_seeds slots: d_nseeds,
+ *    d_rest and d_spans 4-B aligned (n_patterns, n_patterns and 2 S words),
+ *    d_ranges P-aligned (2 S words), d_loc_offsets S + 1 offsets; the same
+ *    rule: exactly that size, no byte outside it touched.
  *  - the workspace: 16-B aligned, fmx_locate_workspace_size(n_patterns)
- *    bytes; a launch may write any of it and nothing outside it.
+ *    bytes (fmx_seeds_batch_async: of n_patterns * max_seeds, one "pattern"
+ *    per slot); a launch may write any of it and nothing outside it.
  *  - cap = 0 with d_locs = NULL sizes an output: the offsets, the counts and
  *    *d_needed are written, no location is. */
 
@@ -370,6 +375,64 @@ fmx_status fmx_match_batch_async(fmx_index *ix, const uint8_t *d_bytes, const ui
                                  uint64_t cap, uint64_t *d_needed, void *d_workspace,
                                  uint64_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------ greedy seed chains
+ * The match above, repeated on the device until the pattern is used up: what
+ * a read mapper does with a read after its first seed (no reference
+ * counterpart).  Added within ABI 8: FMX_ABI_VERSION is unchanged.
+ * Pattern i is p[0..m) in logical order (FMX_PATTERN_REVERSED as for locate).
+ * Parameters: max_seeds (1..32), min_len, skip, max_occ.  With e = m, j = 0,
+ * while e > 0 and j < max_seeds:
+ *  1. (L, lo, hi) = the longest-suffix match of the prefix p[0..e): exactly
+ *     what fmx_match_batch returns for that prefix, same row coordinates.  A
+ *     PassThrough byte >= symbol_count ends a match like any symbol that does
+ *     not occur; nothing is an error of its own (a disagreeing
+ *     FMX_HINT_FIXED_LEN is still FMX_E_ARG).
+ *  2. if L >= max(min_len, 1) this is seed j, covering p[e-L..e): with slot
+ *     s = i * max_seeds + j, spans[2s] = e (its end, exclusive), spans[2s+1] =
+ *     L, ranges[2s], ranges[2s+1] = lo, hi (P-wide); j += 1.
+ *  3. e -= min(e, max(L + skip, 1)).  skip = 0: the non-overlapping cover of
+ *     the pattern; skip = 1 steps over the symbol that failed to extend (a
+ *     substitution); any skip is legal.
+ * Then nseeds[i] = j and rest[i] = e: 0 when the whole pattern was parsed,
+ * else the slots ran out and the caller may resubmit the first rest[i]
+ * symbols.  Every slot j >= nseeds[i] is written as zeros in spans and ranges:
+ * the outputs are fully defined.  An empty pattern: 0 seeds, rest = 0.
+ * out_loc_offsets == NULL (d_loc_offsets == NULL) selects spans and ranges
+ * only: the location arguments and the workspace are ignored.  Otherwise
+ * loc_offsets has n_patterns * max_seeds + 1 entries, one per slot: a stored
+ * seed REPORTS when hi - lo <= max_occ (min_len was applied when it was
+ * stored) and its slot then holds its hi - lo locations in suffix-array-row
+ * order — what fmx_locate_batch returns for that substring; every other slot
+ * holds none.  The capacity contract is fmx_locate_batch's: *needed is always
+ * exact, FMX_E_CAPACITY when it exceeds cap, nothing written past cap; nseeds,
+ * rest, spans, ranges and the offsets are written either way.  The host call
+ * makes one launch with the caller's cap (no retry) and sets the staging and
+ * fixed-length hints itself.  The device call's workspace is
+ * fmx_locate_workspace_size(ix, n_patterns * max_seeds) bytes, 16-B aligned.
+ * FMX_E_ARG: max_seeds outside 1..32, a required pointer that is null, more
+ * slots than a launch's 2^31 - 1 tiles of 256 hold.
+ * One kernel, k_seeds (a lane per pattern, the pattern staged once, the match
+ * restarted on ever shorter prefixes), then the locate's k_emit over the
+ * slots; launch order only; derived structures do not shorten the search (a
+ * loaded full SA serves the locations).  Timer: "seeds", one unit per slot
+ * (n_patterns * max_seeds: how many seeds were stored is not known to the
+ * host when the launch is queued). */
+fmx_status fmx_seeds_batch(fmx_index *ix, const uint8_t *bytes, const uint64_t *offsets,
+                           uint64_t n_patterns, uint32_t flags,
+                           uint32_t max_seeds, uint32_t min_len, uint32_t skip, uint64_t max_occ,
+                           uint32_t *out_nseeds, uint32_t *out_rest,
+                           uint32_t *out_spans, void *out_ranges,
+                           uint64_t *out_loc_offsets, void *out_locs, uint64_t cap,
+                           uint64_t *needed);
+fmx_status fmx_seeds_batch_async(fmx_index *ix, const uint8_t *d_bytes, const uint64_t *d_offsets,
+                                 uint64_t n_patterns, uint32_t flags,
+                                 uint32_t max_seeds, uint32_t min_len, uint32_t skip, uint64_t max_occ,
+                                 uint32_t *d_nseeds, uint32_t *d_rest,
+                                 uint32_t *d_spans, void *d_ranges,
+                                 uint64_t *d_loc_offsets, void *d_locs, uint64_t cap,
+                                 uint64_t *d_needed, void *d_workspace, uint64_t workspace_bytes,
+                                 void *stream);
+
 /* Wait for `stream` and return (and clear) the latched device status. */
 fmx_status fmx_sync(fmx_index *ix, void *stream);
 
@@ -416,7 +479,8 @@ fmx_status fmx_multi_locate_batch(fmx_multi *m, const uint8_t *bytes, const uint
  * durations per kernel since timing was last enabled (enabling resets the
  * totals; fmx_timing_read synchronises).  An event pair costs the stream
  * several microseconds, so throughput runs sample (k > 1).  Timers: "count",
- * "locate" (a whole locate launch), "match" (a whole match launch) and, for
+ * "locate" (a whole locate launch), "match" (a whole match launch), "seeds"
+ * (a whole seed-chain launch, a unit per slot) and, for
  * fmx_locate_group_async, its two kernels "locate.search" (k_search) and
  * "locate.emit" (k_emit). */
 fmx_status fmx_timing_enable(fmx_index *ix, int enable);

@@ -16,6 +16,8 @@ this module                    reference (sview-fmindex/src/...)
 ``FmIndex.locate_batch``
 ``FmIndex.match`` /            (new) longest-suffix match: greedy backward seeding
 ``FmIndex.match_batch``
+``FmIndex.seeds`` /            (new) greedy seed chains: the match restarted on ever shorter prefixes
+``FmIndex.seeds_batch``
 ``FmIndexBuilder``            ``FmIndexBuilder``                builder/mod.rs:59-264 (built on the GPU)
 ``blocks.Block2..Block6``      ``blocks::Block2..Block6<V>``     components/bwm/blocks/
 ``text_encoders.*``            ``EncodingTable`` / ``PassThrough`` components/text_encoder/
@@ -587,6 +589,56 @@ class FmIndex:
         _check(st, "fmx_match_batch")
         return lens[:n], rng[:n], loc_off, locs[:needed.value]
 
+    # -- greedy seed chains (the match restarted until the pattern is used up) --
+    def seeds(self, pattern: bytes, max_seeds: int = 8, min_len: int = 1, skip: int = 0,
+              max_occ: Optional[int] = None) -> List[Tuple[int, int, int, int]]:
+        """The pattern's seeds, right to left: [(end, len, lo, hi)], seed j
+        covering pattern[end - len:end] with suffix-array interval [lo, hi).
+        (max_occ only selects which seeds seeds_batch locates.)"""
+        ns, _, spans, rng = self.seeds_batch([pattern], max_seeds, min_len, skip, max_occ, locate=False)
+        return [(int(spans[0, j, 0]), int(spans[0, j, 1]), int(rng[0, j, 0]), int(rng[0, j, 1]))
+                for j in range(int(ns[0]))]
+
+    def seeds_batch(self, patterns, max_seeds: int = 8, min_len: int = 1, skip: int = 0,
+                    max_occ: Optional[int] = None, reversed: bool = False, locate: bool = True):
+        """Greedy seed chains of many patterns (fmx_seeds_batch): (nseeds
+        uint32[n], rest uint32[n], spans uint32[n, max_seeds, 2], ranges P[n,
+        max_seeds, 2]) and, with `locate`, (..., loc_offsets uint64[n *
+        max_seeds + 1], locations P[total]).  With e = len(p): the longest
+        suffix of p[:e] that occurs in the text, of length L with interval (lo,
+        hi), is a seed when L >= max(min_len, 1) — spans[i, j] = (e, L),
+        ranges[i, j] = (lo, hi) — then e -= min(e, max(L + skip, 1)), until e =
+        0 or max_seeds are stored; rest[i] = the e left (0: all parsed); unused
+        slots are zero.  Slot i * max_seeds + j holds the seed's locations
+        (suffix-array-row order) when hi - lo <= max_occ (None: no bound)."""
+        data, offsets = patterns if isinstance(patterns, tuple) else pack_patterns(patterns)
+        n, ms = offsets.size - 1, int(max_seeds)
+        rows = max(n, 1) * max(ms, 1)
+        ns = np.zeros(max(n, 1), dtype=np.uint32)
+        rest = np.zeros(max(n, 1), dtype=np.uint32)
+        spans = np.zeros((rows, 2), dtype=np.uint32)
+        rng = np.zeros((rows, 2), dtype=self._dt)
+        flags = _n.FMX_PATTERN_REVERSED if reversed else 0
+        occ = (1 << 64) - 1 if max_occ is None else int(max_occ)
+        needed = C.c_uint64()
+        shaped = lambda: (ns[:n], rest[:n], spans[:n * ms].reshape(n, ms, 2),  # noqa: E731
+                          rng[:n * ms].reshape(n, ms, 2))
+        head = (self._h, _ptr(data) if data.size else None, _ptr(offsets), n, flags, ms, int(min_len), int(skip), occ,
+                _ptr(ns), _ptr(rest), _ptr(spans), _ptr(rng))
+        if not locate:
+            _check(_n.lib().fmx_seeds_batch(*head, None, None, 0, C.byref(needed)), "fmx_seeds_batch")
+            return shaped()
+        loc_off = np.zeros(n * max(ms, 0) + 1, dtype=np.uint64)
+        cap = 1 << 16
+        locs = np.zeros(cap, dtype=self._dt)
+        st = _n.lib().fmx_seeds_batch(*head, _ptr(loc_off), _ptr(locs), cap, C.byref(needed))
+        if st == _n.FMX_E_CAPACITY:
+            cap = needed.value
+            locs = np.zeros(max(cap, 1), dtype=self._dt)
+            st = _n.lib().fmx_seeds_batch(*head, _ptr(loc_off), _ptr(locs), cap, C.byref(needed))
+        _check(st, "fmx_seeds_batch")
+        return shaped() + (loc_off, locs[:needed.value])
+
     # -- device-resident API (pointers are ints; stream is a hipStream_t) --
     def count_batch_async(self, d_bytes: int, d_offsets: int, n: int, d_counts: int,
                           stream: int = 0, reversed: bool = False, long_patterns: bool = False, stage_kb: int = 0,
@@ -628,6 +680,24 @@ class FmIndex:
         _check(_n.lib().fmx_match_batch_async(
             self._h, C.c_void_p(d_bytes), C.c_void_p(d_offsets), n, flags, int(min_len),
             (1 << 64) - 1 if max_occ is None else int(max_occ), C.c_void_p(d_lens), C.c_void_p(d_ranges),
+            v(d_loc_offsets), v(d_locs), cap, v(d_needed), v(d_ws), ws_bytes, v(stream)))
+
+    def seeds_batch_async(self, d_bytes: int, d_offsets: int, n: int, d_nseeds: int, d_rest: int, d_spans: int,
+                          d_ranges: int, d_loc_offsets: int = 0, d_locs: int = 0, cap: int = 0, d_needed: int = 0,
+                          d_ws: int = 0, ws_bytes: int = 0, max_seeds: int = 8, min_len: int = 1, skip: int = 0,
+                          max_occ: Optional[int] = None, stream: int = 0, reversed: bool = False,
+                          long_patterns: bool = False, stage_kb: int = 0, fixed_len: int = 0) -> None:
+        """fmx_seeds_batch_async: d_nseeds, d_rest uint32[n], d_spans uint32[2 n
+        max_seeds], d_ranges P[2 n max_seeds]; with d_loc_offsets (uint64[n
+        max_seeds + 1]) also the locations of the reporting seeds, into d_locs
+        (cap entries) with the total in d_needed, over a workspace of
+        locate_workspace_size(n * max_seeds) bytes; d_loc_offsets = 0: spans
+        and intervals only, no workspace."""
+        flags = _flags(reversed, long_patterns, stage_kb, fixed_len)
+        v = lambda x: C.c_void_p(x) if x else None  # noqa: E731
+        _check(_n.lib().fmx_seeds_batch_async(
+            self._h, C.c_void_p(d_bytes), C.c_void_p(d_offsets), n, flags, int(max_seeds), int(min_len), int(skip),
+            (1 << 64) - 1 if max_occ is None else int(max_occ), v(d_nseeds), v(d_rest), v(d_spans), v(d_ranges),
             v(d_loc_offsets), v(d_locs), cap, v(d_needed), v(d_ws), ws_bytes, v(stream)))
 
     @staticmethod

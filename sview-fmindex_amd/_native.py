@@ -97,6 +97,9 @@ SIGNATURES = {
     "fmx_locate_group_async": (_i, [_p, C.POINTER(fmx_locate_job), _u64, _p]),
     "fmx_match_batch": (_i, [_p, _p, _p, _u64, _u32, _u32, _u64, _p, _p, _p, _p, _u64, _PU64]),
     "fmx_match_batch_async": (_i, [_p, _p, _p, _u64, _u32, _u32, _u64, _p, _p, _p, _p, _u64, _p, _p, _u64, _p]),
+    "fmx_seeds_batch": (_i, [_p, _p, _p, _u64, _u32, _u32, _u32, _u32, _u64, _p, _p, _p, _p, _p, _p, _u64, _PU64]),
+    "fmx_seeds_batch_async": (_i, [_p, _p, _p, _u64, _u32, _u32, _u32, _u32, _u64, _p, _p, _p, _p, _p, _p, _u64, _p, _p,
+                                   _u64, _p]),
     "fmx_sync": (_i, [_p, _p]),
     "fmx_stream_release": (_i, [_p, _p]),
     "fmx_multi_load": (_i, [_p, _u64, fmx_layout, C.POINTER(_i), _i, _u32, C.POINTER(_p), _PU64, _PU64]),

@@ -372,6 +372,36 @@ hipError_t launch_match(const fmx_index *ix, const uint8_t *d_bytes, const uint6
                         uint32_t flags, uint32_t min_len, uint64_t max_occ, uint32_t *d_lens, void *d_ranges,
                         uint64_t *d_loc_offsets, void *d_locs, uint64_t cap, uint64_t *d_needed, uint64_t *d_tiles,
                         uint64_t tiles_cap, uint32_t *status, hipStream_t stream);
+// One greedy seed-chain batch (k_seeds; fmx_seeds_batch_async): pattern i owns
+// the max_seeds slots from i * max_seeds.  With tiles (the locate workspace
+// of npat * max_seeds "patterns": G = ceil(npat max_seeds / 256) tile counts, G
+// tile offsets, then a search record per slot) also every slot's record and
+// the tile counts that k_scan / k_emit turn into offsets and locations.
+constexpr uint32_t kMaxSeeds = 32;
+struct SeedBatch {
+    const uint8_t *bytes;
+    const uint64_t *offs;
+    uint64_t npat;
+    uint32_t *out_nseeds;
+    uint32_t *out_rest;
+    uint32_t *out_spans;  // 2 words per slot: end (exclusive), length
+    void *out_rng;        // 2 P-wide words per slot: lo, hi
+    uint64_t *tiles;      // null: spans and intervals only
+    uint64_t max_occ;
+    uint32_t max_seeds;
+    uint32_t min_len;
+    uint32_t skip;
+    uint32_t rev;
+    uint32_t stride;  // FMX_HINT_FIXED_LEN (0: read the offsets)
+};
+// k_seeds, then (d_loc_offsets non-null) k_scan / k_emit over the slots'
+// records: d_tiles as for launch_locate of n * max_seeds patterns.  In launch
+// order only.
+hipError_t launch_seeds(const fmx_index *ix, const uint8_t *d_bytes, const uint64_t *d_offsets, uint64_t n,
+                        uint32_t flags, uint32_t max_seeds, uint32_t min_len, uint32_t skip, uint64_t max_occ,
+                        uint32_t *d_nseeds, uint32_t *d_rest, uint32_t *d_spans, void *d_ranges,
+                        uint64_t *d_loc_offsets, void *d_locs, uint64_t cap, uint64_t *d_needed, uint64_t *d_tiles,
+                        uint64_t tiles_cap, uint32_t *status, hipStream_t stream);
 // `mid` (optional): an event recorded between k_search and k_emit (timing).
 // Fills grp's per-launch fields (first, emit_begin, the grouped fields) in place.
 hipError_t launch_locate_group(const fmx_index *ix, LocateGroup &grp, uint32_t stage_flags,
@@ -502,6 +532,9 @@ struct LayoutOps {
     // longest-suffix match (k_match): every record encoding, no search variant
     hipError_t (*match)(const QueryArgs &qa, uint32_t vb, uint32_t rec, const MatchBatch &mb, uint32_t tiles,
                         uint32_t sb, hipStream_t s);
+    // greedy seed chains (k_seeds): as match
+    hipError_t (*seeds)(const QueryArgs &qa, uint32_t vb, uint32_t rec, const SeedBatch &sb, uint32_t wgs,
+                        uint32_t stage, hipStream_t s);
 };
 uint64_t locate_tiles_cap(uint64_t n);
 // Bytes per pattern of the search-result records in the locate workspace.

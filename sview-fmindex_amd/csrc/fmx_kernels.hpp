@@ -1,5 +1,5 @@
 // fmx_kernels.hpp — the query kernels that depend on the occ layout (P, N,
-// V, record size): k_count, k_search, k_match, k_emit, the deep-table level step, the
+// V, record size): k_count, k_search, k_match, k_seeds, k_emit, the deep-table level step, the
 // full-SA walk and the record re-layout.  Instantiated per (P, N) in its own
 // translation unit (fmx_layout.hip, one object per layout, built in
 // parallel); launched through the LayoutOps table (fmx_internal.hpp).
@@ -423,6 +423,104 @@ __global__ __launch_bounds__(256, 8) void k_match(const QueryArgs a, const Match
         uint64_t agg;
         block_excl_scan(cnt, &agg, s_scan);
         if (threadIdx.x == 0) B.tiles[blockIdx.x] = agg;
+    }
+}
+
+// ------------------------------------------------ k_seeds (greedy seed chain)
+// One lane per pattern, k_match's shape, the pattern staged once: the lane
+// restarts match_suffix on ever shorter prefixes p[0..e) — a smaller m on the
+// same view (an unstaged reversed pattern, whose at(j) reads raw[m-1-j], also
+// has raw advanced by what m lost) — until the pattern or its max_seeds slots
+// are used up (fmx.h: e -= min(e, max(L + skip, 1)); a match of at least
+// max(min_len, 1) symbols is a seed).  Pattern i owns slots [i max_seeds,
+// (i+1) max_seeds): its seeds' (end, length) and (lo, hi) in order, the unused
+// slots zero.  With B.tiles every slot also gets k_emit's record — {lo, count,
+// 0}, the count 0 unless the seed reports (count <= max_occ; unused slots:
+// zeros); one row with a sampled row seen in that restart's own single-row
+// phase (SampledRow), or under a full SA, located here by that one read, any
+// other left to k_emit's walk — and the workgroup, whose slots are exactly max_seeds whole
+// 256-slot tiles of k_emit (the last workgroup's: as many as the batch has),
+// adds each reporting seed's count to its tile's in LDS and writes the tile
+// counts: k_scan / k_emit then run unchanged over npat max_seeds "patterns".
+template <typename P, int N, int VB, int REC>
+__global__ __launch_bounds__(256, 8) void k_seeds(const QueryArgs a, const SeedBatch B, uint32_t stage_bytes) {
+    __shared__ Tables<P> s;
+    FMX_DYN_LDS(s_pat);  // stage_bytes, then the k-mer table (dynamic)
+    __shared__ unsigned long long s_tile[kMaxSeeds];
+    stage_tables(a, s, s_pat + stage_bytes);
+    if (threadIdx.x < kMaxSeeds) s_tile[threadIdx.x] = 0;  // (visible after stage_patterns' barrier)
+    const uint8_t *__restrict__ bytes = B.bytes;
+    const uint64_t npat = B.npat, first = (uint64_t)blockIdx.x * 256u;
+    const bool rev = B.rev != 0;
+    uint64_t beg, end, b0, b1;
+    const bool staged =
+        stage_patterns(s, s_pat, bytes, B.offs, npat, first, rev, stage_bytes, B.stride, a.status, beg, end, b0, b1);
+    __syncthreads();
+    const uint64_t i = first + threadIdx.x;
+    const uint32_t ms = B.max_seeds;
+    const bool loc = B.tiles != nullptr;  // (workgroup-uniform)
+    const uint64_t G = (npat * ms + 255) / 256;  // the batch's 256-slot tiles
+    if (i < npat) {
+        PatView pv = pattern_view(s, s_pat, staged, bytes, beg, end, b0, b1, rev);
+        // Per-lane state kept small (<u32,3,64,*> sit at the 64 VGPRs of 8 waves per SIMD): the outputs
+        // are addressed from the workgroup's first slot (uniform) by a 32-bit slot number, and the
+        // prefix's end e is the view's own m.
+        const uint64_t slot0 = first * ms;
+        uint32_t *__restrict__ spans = B.out_spans + 2 * slot0;
+        P *__restrict__ rng = reinterpret_cast<P *>(B.out_rng) + 2 * slot0;
+        SearchRec<P> *__restrict__ recs = nullptr;
+        if (loc) recs = reinterpret_cast<SearchRec<P> *>(B.tiles + 2 * G) + slot0;
+        uint32_t ls = threadIdx.x * ms;  // seed j's slot in the workgroup: tile ls >> 8 of its max_seeds
+        const uint32_t ls_end = ls + ms;
+        const uint32_t need = B.min_len > 1u ? B.min_len : 1u;
+        const bool raw_rev = rev && !staged;
+        while (pv.m > 0 && ls < ls_end) {
+            P lo, hi;
+            uint32_t len;
+            SampledRow<P> smp;
+            match_suffix<P, N, VB, REC>(a, s, pv, lo, hi, len, smp, loc);
+            if (len >= need) {
+                spans[2 * ls] = (uint32_t)pv.m;
+                spans[2 * ls + 1] = len;
+                rng[2 * ls] = lo;
+                rng[2 * ls + 1] = hi;
+                if (loc) {
+                    const uint64_t cnt = (uint64_t)(hi - lo) <= B.max_occ ? (uint64_t)(hi - lo) : 0;
+                    // one row: located here when that is one read (this restart's sampled row, or the
+                    // full SA); a row that needs the walk is left to k_emit as a one-row interval —
+                    // walk_row inlined here, with the view live across it, spilled in 124 of the 280
+                    // instantiations against 42 without it (k_match: 12), whatever the occupancy bound
+                    P one = 0;
+                    bool settled = false;
+                    if (cnt == 1 && smp.valid) {
+                        one = load_once(reinterpret_cast<const P *>(a.sa) + smp.slot) - smp.off;  // (locate_one)
+                        settled = true;
+                    } else if (cnt == 1 && a.safull != nullptr) {
+                        one = reinterpret_cast<const P *>(a.safull)[(uint64_t)lo * a.sa_stride];  // (walk_row)
+                        settled = true;
+                    }
+                    recs[ls] = settled ? SearchRec<P>{one, P(1), 1ull} : SearchRec<P>{lo, (P)cnt, 0ull};
+                    if (cnt) atomicAdd(&s_tile[ls >> 8], (unsigned long long)cnt);
+                }
+                ++ls;
+            }
+            const uint64_t step = (uint64_t)len + B.skip;
+            const uint64_t cut = step < pv.m ? (step ? step : 1) : pv.m;
+            if (raw_rev) pv.raw += cut;  // (at(j) reads raw[m - 1 - j])
+            pv.m -= cut;
+        }
+        (B.out_nseeds + first)[threadIdx.x] = ms - (ls_end - ls);  // (uniform base + lane: i need not stay live)
+        (B.out_rest + first)[threadIdx.x] = (uint32_t)pv.m;
+        for (; ls < ls_end; ++ls) {
+            spans[2 * ls] = spans[2 * ls + 1] = 0;
+            rng[2 * ls] = rng[2 * ls + 1] = 0;
+            if (loc) recs[ls] = SearchRec<P>{P(0), P(0), 0ull};
+        }
+    }
+    if (loc) {
+        __syncthreads();
+        const uint64_t tile = (uint64_t)blockIdx.x * ms + threadIdx.x;
+        if (threadIdx.x < ms && tile < G) B.tiles[tile] = s_tile[threadIdx.x];
     }
 }
 
