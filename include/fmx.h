@@ -247,9 +247,14 @@ fmx_status fmx_locate_batch(fmx_index *ix, const uint8_t *bytes, const uint64_t 
  *    d_rest and d_spans 4-B aligned (n_patterns, n_patterns and 2 S words),
  *    d_ranges P-aligned (2 S words), d_loc_offsets S + 1 offsets; the same
  *    rule: exactly that size, no byte outside it touched.
+ *    fmx_approx_batch_async, with S = n_patterns * max_hits slots: d_nhits,
+ *    d_more, d_mm and d_subs 4-B aligned (n_patterns, n_patterns, S and 6 S
+ *    words), d_ranges P-aligned (2 S words), d_loc_offsets S + 1 offsets;
+ *    the same rule again.
  *  - the workspace: 16-B aligned, fmx_locate_workspace_size(n_patterns)
- *    bytes (fmx_seeds_batch_async: of n_patterns * max_seeds, one "pattern"
- *    per slot); a launch may write any of it and nothing outside it.
+ *    bytes (fmx_seeds_batch_async: of n_patterns * max_seeds, and
+ *    fmx_approx_batch_async: of n_patterns * max_hits, one "pattern" per
+ *    slot); a launch may write any of it and nothing outside it.
  *  - cap = 0 with d_locs = NULL sizes an output: the offsets, the counts and
  *    *d_needed are written, no location is. */
 
@@ -433,6 +438,80 @@ fmx_status fmx_seeds_batch_async(fmx_index *ix, const uint8_t *d_bytes, const ui
                                  uint64_t *d_needed, void *d_workspace, uint64_t workspace_bytes,
                                  void *stream);
 
+/* ------------------------------------------------------- k-mismatch search
+ * Search within a Hamming radius: what a read mapper's -v mode asks of an
+ * FM-index (no reference counterpart).  Added within ABI 8: FMX_ABI_VERSION
+ * is unchanged.
+ * Pattern i is p[0..m) in logical order (FMX_PATTERN_REVERSED as for locate),
+ * c_q = idx_of(p[q]).  Parameters: max_mm (0..3), max_hits (1..32), max_occ,
+ * mode (0 or FMX_APPROX_BEST).
+ * A VARIANT is a string v of m symbol indices that differs from the pattern
+ * in d <= max_mm positions and occurs in the encoded text.  Substitutions
+ * only, no insertions or deletions.  A position with c_q >= symbol_count (a
+ * PassThrough byte out of range) can only be matched by substituting it; like
+ * every other case here it is no error of its own (a disagreeing
+ * FMX_HINT_FIXED_LEN is still FMX_E_ARG).  A substituted symbol ranges over
+ * all of 0..symbol_count-1 except c_q; symbols that do not occur in the text
+ * simply give no variant.  m = 0 gives no variant, and neither does an m
+ * longer than the text.
+ * ORDER: by d ascending; within one d, scan the positions from m-1 down to 0:
+ * at the first position where two variants differ, the one that holds a
+ * substituted symbol comes before the one that holds the pattern's own, and
+ * of two substituted symbols the smaller index comes first.  (The order in
+ * which a right-to-left depth-first search meets them when it tries the
+ * substitutions of a position in ascending symbol order before the pattern's
+ * own symbol.)
+ * FMX_APPROX_BEST keeps only the variants of the smallest d that has any (a
+ * mapper's "best stratum").  With H variants after that filter, nhits[i] =
+ * min(H, max_hits) and more[i] = (H > max_hits); the search stops at the
+ * (max_hits+1)-th variant and never computes H.
+ * Pattern i owns slots s = i * max_hits + j, j < nhits[i] in the order above:
+ * ranges[2s], ranges[2s+1] = lo, hi (P-wide, the reduced row coordinates of
+ * get_pos_range: what fmx_match_batch reports for a pattern equal to v);
+ * mm[s] = d; substitution t < d, listed by decreasing position, is subs[2(3s +
+ * t)] = its position (logical order) and subs[2(3s+t)+1] = the substituted
+ * symbol index.  Everything else in a pattern's slots is written as zeros —
+ * t >= d and j >= nhits[i], in mm, subs and ranges: the outputs are fully
+ * defined.
+ * Locations follow the rules of seeds.  out_loc_offsets == NULL
+ * (d_loc_offsets == NULL) selects intervals only: the location arguments and
+ * the workspace are ignored.  Otherwise loc_offsets has n_patterns * max_hits
+ * + 1 entries: a stored hit REPORTS when hi - lo <= max_occ, and its slot then
+ * holds its hi - lo locations in suffix-array-row order — what
+ * fmx_locate_batch returns for v; every other slot holds none.  The capacity
+ * contract is fmx_locate_batch's: *needed is always exact, FMX_E_CAPACITY when
+ * it exceeds cap, nothing written past cap; all other outputs are written
+ * either way.  The host call makes one launch with the caller's cap (no
+ * retry) and sets the staging and fixed-length hints itself.  The device
+ * call's workspace is fmx_locate_workspace_size(ix, n_patterns * max_hits)
+ * bytes, 16-B aligned.
+ * FMX_E_ARG: max_mm > 3, max_hits outside 1..32, unknown mode bits, a required
+ * pointer that is null, more slots than a launch's 2^31 - 1 tiles of 256 hold.
+ * COST: a bounded backtracking walk per pattern.  On repetitive text the work
+ * grows like (m * symbol_count)^max_mm LF steps per pattern; the caller bounds
+ * it with max_mm and max_hits (a search ends at its (max_hits+1)-th variant).
+ * There is no step budget in this version.
+ * One kernel, k_approx (a lane per pattern, the pattern staged once, stratum
+ * by stratum), then the locate's k_emit over the slots; launch order only;
+ * derived structures do not shorten the search (a loaded full SA serves the
+ * locations).  Timer: "approx", one unit per slot. */
+#define FMX_APPROX_BEST 1u /* mode: only the variants of the smallest d that has any */
+fmx_status fmx_approx_batch(fmx_index *ix, const uint8_t *bytes, const uint64_t *offsets,
+                            uint64_t n_patterns, uint32_t flags,
+                            uint32_t max_mm, uint32_t max_hits, uint32_t mode, uint64_t max_occ,
+                            uint32_t *out_nhits, uint32_t *out_more,
+                            uint32_t *out_mm, uint32_t *out_subs, void *out_ranges,
+                            uint64_t *out_loc_offsets, void *out_locs, uint64_t cap,
+                            uint64_t *needed);
+fmx_status fmx_approx_batch_async(fmx_index *ix, const uint8_t *d_bytes, const uint64_t *d_offsets,
+                                  uint64_t n_patterns, uint32_t flags,
+                                  uint32_t max_mm, uint32_t max_hits, uint32_t mode, uint64_t max_occ,
+                                  uint32_t *d_nhits, uint32_t *d_more,
+                                  uint32_t *d_mm, uint32_t *d_subs, void *d_ranges,
+                                  uint64_t *d_loc_offsets, void *d_locs, uint64_t cap,
+                                  uint64_t *d_needed, void *d_workspace, uint64_t workspace_bytes,
+                                  void *stream);
+
 /* Wait for `stream` and return (and clear) the latched device status. */
 fmx_status fmx_sync(fmx_index *ix, void *stream);
 
@@ -480,7 +559,8 @@ fmx_status fmx_multi_locate_batch(fmx_multi *m, const uint8_t *bytes, const uint
  * totals; fmx_timing_read synchronises).  An event pair costs the stream
  * several microseconds, so throughput runs sample (k > 1).  Timers: "count",
  * "locate" (a whole locate launch), "match" (a whole match launch), "seeds"
- * (a whole seed-chain launch, a unit per slot) and, for
+ * (a whole seed-chain launch, a unit per slot), "approx" (a whole k-mismatch
+ * launch, a unit per slot) and, for
  * fmx_locate_group_async, its two kernels "locate.search" (k_search) and
  * "locate.emit" (k_emit). */
 fmx_status fmx_timing_enable(fmx_index *ix, int enable);

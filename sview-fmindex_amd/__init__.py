@@ -18,6 +18,8 @@ this module                    reference (sview-fmindex/src/...)
 ``FmIndex.match_batch``
 ``FmIndex.seeds`` /            (new) greedy seed chains: the match restarted on ever shorter prefixes
 ``FmIndex.seeds_batch``
+``FmIndex.approx`` /           (new) k-mismatch search: every variant within max_mm substitutions
+``FmIndex.approx_batch``
 ``FmIndexBuilder``            ``FmIndexBuilder``                builder/mod.rs:59-264 (built on the GPU)
 ``blocks.Block2..Block6``      ``blocks::Block2..Block6<V>``     components/bwm/blocks/
 ``text_encoders.*``            ``EncodingTable`` / ``PassThrough`` components/text_encoder/
@@ -639,6 +641,63 @@ class FmIndex:
         _check(st, "fmx_seeds_batch")
         return shaped() + (loc_off, locs[:needed.value])
 
+    # -- k-mismatch search (substitutions only, a bounded backtracking walk on the device) --
+    def approx(self, pattern: bytes, max_mm: int = 1, max_hits: int = 8,
+               best: bool = False) -> List[Tuple[int, List[Tuple[int, int]], int, int]]:
+        """The pattern's variants within max_mm substitutions that occur in
+        the text, in the contract's order: [(d, [(pos, sym), ...], lo, hi)],
+        the d substitutions by decreasing position (sym a symbol index), [lo,
+        hi) the variant's suffix-array interval; at most max_hits of them."""
+        nh, _, mm, subs, rng = self.approx_batch([pattern], max_mm, max_hits, best, locate=False)
+        return [(int(mm[0, j]), [(int(subs[0, j, t, 0]), int(subs[0, j, t, 1])) for t in range(int(mm[0, j]))],
+                 int(rng[0, j, 0]), int(rng[0, j, 1])) for j in range(int(nh[0]))]
+
+    def approx_batch(self, patterns, max_mm: int = 1, max_hits: int = 8, best: bool = False,
+                     max_occ: Optional[int] = None, reversed: bool = False, locate: bool = True):
+        """k-mismatch search of many patterns (fmx_approx_batch): (nhits
+        uint32[n], more uint32[n], mm uint32[n, max_hits], subs uint32[n,
+        max_hits, 3, 2], ranges P[n, max_hits, 2]) and, with `locate`, (...,
+        loc_offsets uint64[n * max_hits + 1], locations P[total]).  A variant
+        differs from the pattern in d <= max_mm positions (substitutions only)
+        and occurs in the text; they come by d ascending, then — scanning the
+        positions from the last to the first — a substituted symbol before the
+        pattern's own, a smaller substituted symbol first.  `best` keeps the
+        smallest d that has any.  nhits[i] of them are stored (more[i]: there
+        are others): mm[i, j] = d, subs[i, j, t] = (position, symbol index) of
+        substitution t < d by decreasing position, ranges[i, j] = (lo, hi);
+        unused entries are zero.  Slot i * max_hits + j holds the variant's
+        locations (suffix-array-row order) when hi - lo <= max_occ (None: no
+        bound)."""
+        data, offsets = patterns if isinstance(patterns, tuple) else pack_patterns(patterns)
+        n, mh = offsets.size - 1, int(max_hits)
+        rows = max(n, 1) * max(mh, 1)
+        nh = np.zeros(max(n, 1), dtype=np.uint32)
+        more = np.zeros(max(n, 1), dtype=np.uint32)
+        mm = np.zeros(rows, dtype=np.uint32)
+        subs = np.zeros((rows, 6), dtype=np.uint32)
+        rng = np.zeros((rows, 2), dtype=self._dt)
+        flags = _n.FMX_PATTERN_REVERSED if reversed else 0
+        mode = _n.FMX_APPROX_BEST if best else 0
+        occ = (1 << 64) - 1 if max_occ is None else int(max_occ)
+        needed = C.c_uint64()
+        shaped = lambda: (nh[:n], more[:n], mm[:n * mh].reshape(n, mh),  # noqa: E731
+                          subs[:n * mh].reshape(n, mh, 3, 2), rng[:n * mh].reshape(n, mh, 2))
+        head = (self._h, _ptr(data) if data.size else None, _ptr(offsets), n, flags, int(max_mm), mh, mode, occ,
+                _ptr(nh), _ptr(more), _ptr(mm), _ptr(subs), _ptr(rng))
+        if not locate:
+            _check(_n.lib().fmx_approx_batch(*head, None, None, 0, C.byref(needed)), "fmx_approx_batch")
+            return shaped()
+        loc_off = np.zeros(n * max(mh, 0) + 1, dtype=np.uint64)
+        cap = 1 << 16
+        locs = np.zeros(cap, dtype=self._dt)
+        st = _n.lib().fmx_approx_batch(*head, _ptr(loc_off), _ptr(locs), cap, C.byref(needed))
+        if st == _n.FMX_E_CAPACITY:
+            cap = needed.value
+            locs = np.zeros(max(cap, 1), dtype=self._dt)
+            st = _n.lib().fmx_approx_batch(*head, _ptr(loc_off), _ptr(locs), cap, C.byref(needed))
+        _check(st, "fmx_approx_batch")
+        return shaped() + (loc_off, locs[:needed.value])
+
     # -- device-resident API (pointers are ints; stream is a hipStream_t) --
     def count_batch_async(self, d_bytes: int, d_offsets: int, n: int, d_counts: int,
                           stream: int = 0, reversed: bool = False, long_patterns: bool = False, stage_kb: int = 0,
@@ -699,6 +758,25 @@ class FmIndex:
             self._h, C.c_void_p(d_bytes), C.c_void_p(d_offsets), n, flags, int(max_seeds), int(min_len), int(skip),
             (1 << 64) - 1 if max_occ is None else int(max_occ), v(d_nseeds), v(d_rest), v(d_spans), v(d_ranges),
             v(d_loc_offsets), v(d_locs), cap, v(d_needed), v(d_ws), ws_bytes, v(stream)))
+
+    def approx_batch_async(self, d_bytes: int, d_offsets: int, n: int, d_nhits: int, d_more: int, d_mm: int,
+                           d_subs: int, d_ranges: int, d_loc_offsets: int = 0, d_locs: int = 0, cap: int = 0,
+                           d_needed: int = 0, d_ws: int = 0, ws_bytes: int = 0, max_mm: int = 1, max_hits: int = 8,
+                           best: bool = False, max_occ: Optional[int] = None, stream: int = 0, reversed: bool = False,
+                           long_patterns: bool = False, stage_kb: int = 0, fixed_len: int = 0) -> None:
+        """fmx_approx_batch_async: d_nhits, d_more uint32[n], d_mm uint32[n
+        max_hits], d_subs uint32[6 n max_hits], d_ranges P[2 n max_hits]; with
+        d_loc_offsets (uint64[n max_hits + 1]) also the locations of the
+        reporting hits, into d_locs (cap entries) with the total in d_needed,
+        over a workspace of locate_workspace_size(n * max_hits) bytes;
+        d_loc_offsets = 0: intervals only, no workspace."""
+        flags = _flags(reversed, long_patterns, stage_kb, fixed_len)
+        v = lambda x: C.c_void_p(x) if x else None  # noqa: E731
+        _check(_n.lib().fmx_approx_batch_async(
+            self._h, C.c_void_p(d_bytes), C.c_void_p(d_offsets), n, flags, int(max_mm), int(max_hits),
+            _n.FMX_APPROX_BEST if best else 0, (1 << 64) - 1 if max_occ is None else int(max_occ), v(d_nhits),
+            v(d_more), v(d_mm), v(d_subs), v(d_ranges), v(d_loc_offsets), v(d_locs), cap, v(d_needed), v(d_ws),
+            ws_bytes, v(stream)))
 
     @staticmethod
     def locate_job(d_bytes: int, d_offsets: int, n: int, d_loc_offsets: int, d_locs: int, cap: int,

@@ -28,6 +28,7 @@ FMX_ENC_TABLE = 0
 FMX_ENC_PASS = 1
 FMX_PATTERN_REVERSED = 1
 FMX_HINT_LONG_PATTERNS = 2
+FMX_APPROX_BEST = 1
 FMX_OCC_BLOB = 0
 FMX_OCC_INTERLEAVED = 1
 FMX_OPT_DEEP_LUT = 2
@@ -100,6 +101,10 @@ SIGNATURES = {
     "fmx_seeds_batch": (_i, [_p, _p, _p, _u64, _u32, _u32, _u32, _u32, _u64, _p, _p, _p, _p, _p, _p, _u64, _PU64]),
     "fmx_seeds_batch_async": (_i, [_p, _p, _p, _u64, _u32, _u32, _u32, _u32, _u64, _p, _p, _p, _p, _p, _p, _u64, _p, _p,
                                    _u64, _p]),
+    "fmx_approx_batch": (_i, [_p, _p, _p, _u64, _u32, _u32, _u32, _u32, _u64, _p, _p, _p, _p, _p, _p, _p, _u64,
+                              _PU64]),
+    "fmx_approx_batch_async": (_i, [_p, _p, _p, _u64, _u32, _u32, _u32, _u32, _u64, _p, _p, _p, _p, _p, _p, _p, _u64, _p,
+                                    _p, _u64, _p]),
     "fmx_sync": (_i, [_p, _p]),
     "fmx_stream_release": (_i, [_p, _p]),
     "fmx_multi_load": (_i, [_p, _u64, fmx_layout, C.POINTER(_i), _i, _u32, C.POINTER(_p), _PU64, _PU64]),

@@ -1284,6 +1284,46 @@ fmx_status fmx_seeds_batch_async(fmx_index *ix, const uint8_t *d_bytes, const ui
     });
 }
 
+// max_mm, max_hits and mode in range and a slot count (n * max_hits) whose
+// 256-slot tiles a launch takes (as seeds_shape_ok)
+static bool approx_shape_ok(uint64_t n, uint32_t max_mm, uint32_t max_hits, uint32_t mode) {
+    if (max_mm > kMaxMismatch || max_hits < 1 || max_hits > kMaxHits || (mode & ~FMX_APPROX_BEST)) return false;
+    return n <= (0x7FFFFFFFull * 256) / max_hits;
+}
+
+fmx_status fmx_approx_batch_async(fmx_index *ix, const uint8_t *d_bytes, const uint64_t *d_offsets, uint64_t n,
+                                  uint32_t flags, uint32_t max_mm, uint32_t max_hits, uint32_t mode, uint64_t max_occ,
+                                  uint32_t *d_nhits, uint32_t *d_more, uint32_t *d_mm, uint32_t *d_subs,
+                                  void *d_ranges, uint64_t *d_loc_offsets, void *d_locs, uint64_t cap,
+                                  uint64_t *d_needed, void *d_ws, uint64_t ws_bytes, void *stream) {
+    if (!ix || !approx_shape_ok(n, max_mm, max_hits, mode)) return FMX_E_ARG;
+    if (n && (!d_bytes || !d_offsets || !d_nhits || !d_more || !d_mm || !d_subs || !d_ranges)) return FMX_E_ARG;
+    const bool loc = d_loc_offsets != nullptr;  // (else: intervals only, no workspace)
+    const uint64_t slots = n * max_hits;
+    if (loc) {
+        if (!d_needed || (cap && !d_locs)) return FMX_E_ARG;
+        if (!d_ws || ws_bytes < kWsHeader + 16 || ((uintptr_t)d_ws & 15) != 0) return FMX_E_ARG;
+        if (n && ws_bytes < ws_bytes_for(ix, slots)) return FMX_E_ARG;
+    }
+    hipStream_t s = stream ? (hipStream_t)stream : ix->stream;
+    DeviceGuard dg(ix->device);
+    if (n == 0) {
+        if (!loc) return FMX_OK;
+        hipError_t e = hipMemsetAsync(d_loc_offsets, 0, 8, s);
+        if (e == hipSuccess) e = hipMemsetAsync(d_needed, 0, 8, s);
+        return dev_err(e);
+    }
+    uint8_t *ws = (uint8_t *)d_ws;
+    const uint64_t G = locate_tiles_cap(slots);
+    return with_status(ix, s, [&](uint32_t *status) {
+        return dev_err(timed(ix, "approx", s, slots, [&] {
+            return launch_approx(ix, d_bytes, d_offsets, n, flags, max_mm, max_hits, mode, max_occ, d_nhits, d_more,
+                                 d_mm, d_subs, d_ranges, d_loc_offsets, d_locs, cap, d_needed,
+                                 loc ? (uint64_t *)(ws + kWsHeader) : nullptr, G, status, s);
+        }));
+    });
+}
+
 fmx_status fmx_locate_jobs_async(fmx_index *ix, const fmx_locate_job *jobs, uint64_t n_jobs) {
     if (!ix || (n_jobs && !jobs)) return FMX_E_ARG;
     for (uint64_t i = 0; i < n_jobs; ++i) {
@@ -1623,6 +1663,71 @@ fmx_status fmx_seeds_batch(fmx_index *ix, const uint8_t *bytes, const uint64_t *
     e = ix->stage.d2h(out_nseeds, d + o_ns, n * 4, s);
     if (e == hipSuccess) e = ix->stage.d2h(out_rest, d + o_rest, n * 4, s);
     if (e == hipSuccess) e = ix->stage.d2h(out_spans, d + o_span, 2 * slots * 4, s);
+    if (e == hipSuccess) e = ix->stage.d2h(out_ranges, d + o_rng, 2 * slots * pb, s);
+    if (e == hipSuccess && loc) e = ix->stage.d2h(out_loc_offsets, d + o_loff, (slots + 1) * 8, s);
+    if (e != hipSuccess) return FMX_E_DEVICE;
+    if (total > cap) return FMX_E_CAPACITY;
+    if (total) e = ix->stage.d2h(out_locs, d + o_locs, total * pb, s);
+    return dev_err(e);
+}
+
+// k-mismatch search of a host batch: upload, one fmx_approx_batch_async over
+// the index's scratch and workspace, download.  No retry, as fmx_seeds_batch.
+fmx_status fmx_approx_batch(fmx_index *ix, const uint8_t *bytes, const uint64_t *offsets, uint64_t n, uint32_t flags,
+                            uint32_t max_mm, uint32_t max_hits, uint32_t mode, uint64_t max_occ, uint32_t *out_nhits,
+                            uint32_t *out_more, uint32_t *out_mm, uint32_t *out_subs, void *out_ranges,
+                            uint64_t *out_loc_offsets, void *out_locs, uint64_t cap, uint64_t *needed) {
+    const bool loc = out_loc_offsets != nullptr;
+    if (!ix || !approx_shape_ok(n, max_mm, max_hits, mode)) return FMX_E_ARG;
+    if ((n && (!offsets || !out_nhits || !out_more || !out_mm || !out_subs || !out_ranges)) ||
+        (loc && cap && !out_locs))
+        return FMX_E_ARG;
+    if (needed) *needed = 0;
+    if (n == 0) {
+        if (loc) out_loc_offsets[0] = 0;
+        return FMX_OK;
+    }
+    if (offsets[0] != 0) return FMX_E_ARG;
+    for (uint64_t i = 0; i < n; ++i)
+        if (offsets[i + 1] < offsets[i]) return FMX_E_ARG;
+    if (offsets[n] && !bytes) return FMX_E_ARG;
+    std::lock_guard<std::mutex> g(ix->mu);
+    DeviceGuard dg(ix->device);
+    const uint64_t nb = offsets[n], pb = ix->bv.L.pos_bytes, slots = n * max_hits;
+    flags = (flags & 0xffu) | stage_hint(offsets, n);
+    fmx_status st = loc ? ensure_ws(ix, slots) : FMX_OK;
+    if (st) return st;
+    const uint64_t o_off = align_up(std::max<uint64_t>(nb, 1), 256);
+    const uint64_t o_nh = o_off + align_up((n + 1) * 8, 256);
+    const uint64_t o_more = o_nh + align_up(n * 4, 256);
+    const uint64_t o_mm = o_more + align_up(n * 4, 256);
+    const uint64_t o_subs = o_mm + align_up(slots * 4, 256);
+    const uint64_t o_rng = o_subs + align_up(6 * slots * 4, 256);
+    const uint64_t o_loff = o_rng + align_up(2 * slots * pb, 256);
+    const uint64_t o_need = o_loff + align_up((slots + 1) * 8, 256);
+    const uint64_t o_locs = o_need + 256;
+    if (loc && cap > (~0ull - o_locs) / pb) return FMX_E_ARG;
+    hipStream_t s = ix->stream;
+    st = ensure_scratch(ix, loc ? o_locs + std::max<uint64_t>(cap, 1) * pb : o_loff);
+    if (st) return st;
+    uint8_t *d = ix->d_scratch;
+    hipError_t e = ix->stage.h2d(d, bytes, nb, s);
+    if (e == hipSuccess) e = ix->stage.h2d(d + o_off, offsets, (n + 1) * 8, s);
+    if (e != hipSuccess) return FMX_E_DEVICE;
+    st = fmx_approx_batch_async(ix, d, (uint64_t *)(d + o_off), n, flags, max_mm, max_hits, mode, max_occ,
+                                (uint32_t *)(d + o_nh), (uint32_t *)(d + o_more), (uint32_t *)(d + o_mm),
+                                (uint32_t *)(d + o_subs), d + o_rng, loc ? (uint64_t *)(d + o_loff) : nullptr,
+                                d + o_locs, cap, (uint64_t *)(d + o_need), ix->d_ws, ix->ws_bytes, s);
+    if (st) return st;
+    uint64_t total = 0;
+    if (loc && ix->stage.d2h(&total, d + o_need, 8, s) != hipSuccess) return FMX_E_DEVICE;
+    st = read_status(ix, s);
+    if (st) return st;
+    if (needed) *needed = total;
+    e = ix->stage.d2h(out_nhits, d + o_nh, n * 4, s);
+    if (e == hipSuccess) e = ix->stage.d2h(out_more, d + o_more, n * 4, s);
+    if (e == hipSuccess) e = ix->stage.d2h(out_mm, d + o_mm, slots * 4, s);
+    if (e == hipSuccess) e = ix->stage.d2h(out_subs, d + o_subs, 6 * slots * 4, s);
     if (e == hipSuccess) e = ix->stage.d2h(out_ranges, d + o_rng, 2 * slots * pb, s);
     if (e == hipSuccess && loc) e = ix->stage.d2h(out_loc_offsets, d + o_loff, (slots + 1) * 8, s);
     if (e != hipSuccess) return FMX_E_DEVICE;

@@ -1117,6 +1117,164 @@ FMX_HD void match_suffix(const QueryArgs &a, const Tables<P> &s, const PatView &
     }
 }
 
+// One open substitution of the k-mismatch search (approx_search): the position
+// it stands at, the symbol it holds and the interval of the variant's symbols
+// to the right of it.
+template <typename P>
+struct ApproxFrame {
+    uint32_t pos;  // the substituted position (pattern order)
+    uint32_t w;    // the pattern's own symbol << 16 | the next substitute to try (the one held, plus 1)
+    P lo, hi;      // interval of v(pos..m) (pos = m - 1: none yet, the step is the table's)
+    FMX_HD uint32_t sym() const { return (w & 0xffffu) - 1u; }
+};
+
+// k-mismatch search (fmx.h, "k-mismatch search"): every string v of m symbol
+// indices that differs from the pattern in at most max_mm positions and occurs
+// in the text, with its interval in the coordinates of get_pos_range, handed to
+// emit(d, lo, hi, f0, f1, f2) in the contract's order (f_t, t < d: v's
+// substitutions by decreasing position); emit returns true to end the search.
+// Stratum by stratum, d = 0, 1, ..: variants with exactly d substitutions, by a
+// right-to-left depth-first walk that tries a position's substitutes in
+// ascending symbol order before the pattern's own symbol — which is the
+// contract's order within a stratum: two variants agree to the right of the
+// first position (from m - 1 down) where they differ, so they share the walk's
+// path down to it, where the substitutes come first, in symbol order.  `best`
+// ends the search after the first stratum that has a variant.
+// The walk's state is d frames, not an interval per position: frame t holds the
+// t-th substitution; when its substitutes at pos are used up it takes the
+// pattern's own symbol there and slides to pos - 1.  One loop, one LF step per
+// round (the k-mer table's one-symbol form for position m - 1), of three kinds:
+// a substitute tried (kSubst), a frame slid (kSlide), and — all d substitutions
+// placed — the pattern's own symbols down to 0 (kExact), the next one fetched a
+// step ahead as search_seeded does.  A branch ends when its interval is empty,
+// at an own symbol >= sigma, and when fewer positions remain than substitutions
+// are owed.  The d = 0 stratum is the exact search, seeded with the pattern's
+// last min(m, k) symbols (count_array.rs:203-233); later strata take single
+// steps.  The blob's k-mer table and occ records only.
+template <typename P, int N, int VB, int REC, typename Emit>
+FMX_HD void approx_search(const QueryArgs &a, const Tables<P> &s, const PatView &pv, uint32_t max_mm, bool best,
+                          Emit &&emit) {
+    using O = Occ<P, N, VB, REC>;
+    using F = ApproxFrame<P>;
+    constexpr uint32_t kExact = 0, kSubst = 1, kSlide = 2;
+    const uint32_t sigma = a.sigma, k = a.k;
+    const P sent = (P)a.sentinel;
+    if (pv.m == 0 || pv.m > a.n || pv.m > 0xFFFFFFFFull) return;  // (longer than the text: no variant)
+    const uint32_t m = (uint32_t)pv.m;
+    // three named frames, picked by selects field by field: a runtime-indexed array would go to scratch,
+    // and so does a select between whole structs (it is one between their addresses)
+    F f0{0u, 0u, P(0), P(0)}, f1 = f0, f2 = f0;
+    auto sel = [](uint32_t t, auto x0, auto x1, auto x2) { return t == 0 ? x0 : (t == 1 ? x1 : x2); };
+    auto fget = [&](uint32_t t) -> F {
+        return F{sel(t, f0.pos, f1.pos, f2.pos), sel(t, f0.w, f1.w, f2.w), sel(t, f0.lo, f1.lo, f2.lo),
+                 sel(t, f0.hi, f1.hi, f2.hi)};
+    };
+    auto put = [](F &f, bool on, const F &v) {  // (a conditional store is a select between addresses again)
+        f.pos = on ? v.pos : f.pos;
+        f.w = on ? v.w : f.w;
+        f.lo = on ? v.lo : f.lo;
+        f.hi = on ? v.hi : f.hi;
+    };
+    auto fset = [&](uint32_t t, const F &v) {
+        put(f0, t == 0, v);
+        put(f1, t == 1, v);
+        put(f2, t >= 2, v);
+    };
+    bool any = false;
+    for (uint32_t d = 0; d <= max_mm && d <= m; ++d) {
+        P lo = 0, hi = 0;
+        uint32_t idx = m, nd = 0;
+        bool back = false;  // the branch is over: advance the innermost frame
+        if (d == 0) {
+            const uint32_t take = m < k ? m : k;
+            uint64_t code = 0;
+            uint32_t bad = 0;
+            for (uint32_t j = 0; j < take; ++j) {
+                const uint32_t c = pv.at(m - take + j);
+                bad |= c >= sigma;
+                code += (uint64_t)(c + 1) * s.mult[j];
+            }
+            if (bad) continue;  // (a symbol >= sigma is only matched by substituting it)
+            lo = s.kt[code - 1];
+            hi = s.kt[m < k ? code + s.mult[m - 1] - 1 : code];
+            idx = m - take;
+            back = !(lo < hi);
+        }
+        uint32_t cn = idx > 0 ? pv.at(idx - 1) : 0;  // the pattern's symbol at idx - 1, fetched one step ahead
+        for (;;) {
+            if (!back && nd == d && idx == 0) {
+                any = true;
+                if (emit(d, lo, hi, f0, f1, f2)) return;
+                back = true;
+            }
+            if (!back && nd < d) {  // the next substitution's frame opens at idx - 1
+                if (idx >= d - nd) {
+                    fset(nd, F{idx - 1, cn << 16, lo, hi});
+                    ++nd;
+                }
+                back = true;
+            }
+            uint32_t kind = kExact, c = cn, t = 0, spos = idx - 1;
+            P slo = lo, shi = hi;
+            if (back) {
+                if (nd == 0) break;
+                t = nd - 1;
+                F f = fget(t);
+                const uint32_t cq = f.w >> 16;
+                uint32_t sym = f.w & 0xffffu;
+                if (sym == cq) ++sym;
+                if (sym < sigma) {
+                    kind = kSubst;
+                    c = sym;
+                    const uint32_t nw = (cq << 16) | (sym + 1);
+                    f0.w = t == 0 ? nw : f0.w;
+                    f1.w = t == 1 ? nw : f1.w;
+                    f2.w = t >= 2 ? nw : f2.w;
+                } else {
+                    if (cq >= sigma || f.pos < d - t) {  // (no own symbol to take, or no room further left)
+                        nd = t;
+                        continue;
+                    }
+                    kind = kSlide;
+                    c = cq;
+                }
+                spos = f.pos;
+                slo = f.lo;
+                shi = f.hi;
+            } else if (c >= sigma) {
+                back = true;
+                continue;
+            }
+            P nlo, nhi;
+            if (spos == m - 1) {  // the rightmost symbol: the k-mers that start with it (match_suffix's t = 1)
+                const uint64_t code = (uint64_t)(c + 1) * s.mult[0];
+                nlo = s.kt[code - 1];
+                nhi = s.kt[code + s.mult[0] - 1];
+                cn = spos > 0 ? pv.at(spos - 1) : 0;
+            } else {
+                const P plo = slo + (slo < sent ? P(1) : P(0));  // bwm/mod.rs:202-204
+                const P phi = shi + (shi < sent ? P(1) : P(0));
+                P rlo, rhi;
+                O::rank_pair(a, plo, phi, c, rlo, rhi);
+                const P pre = s.C[c];
+                cn = spos > 0 ? pv.at(spos - 1) : 0;
+                nlo = pre + rlo;
+                nhi = pre + rhi;
+            }
+            if (kind == kSlide) {
+                if (nlo < nhi) fset(t, F{spos - 1, cn << 16, nlo, nhi});
+                else nd = t;
+            } else {
+                lo = nlo;
+                hi = nhi;
+                idx = spos;
+                back = !(nlo < nhi);
+            }
+        }
+        if (best && any) break;
+    }
+}
+
 // A value read once by one lane (the sampled-SA entry of a walk): a
 // non-temporal load on the device, so that its line does not displace the
 // occ records that other patterns read again.

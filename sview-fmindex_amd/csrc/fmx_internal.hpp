@@ -402,6 +402,36 @@ hipError_t launch_seeds(const fmx_index *ix, const uint8_t *d_bytes, const uint6
                         uint32_t *d_nseeds, uint32_t *d_rest, uint32_t *d_spans, void *d_ranges,
                         uint64_t *d_loc_offsets, void *d_locs, uint64_t cap, uint64_t *d_needed, uint64_t *d_tiles,
                         uint64_t tiles_cap, uint32_t *status, hipStream_t stream);
+// One k-mismatch batch (k_approx; fmx_approx_batch_async): pattern i owns the
+// max_hits slots from i * max_hits, tiles as for SeedBatch (the locate
+// workspace of npat * max_hits "patterns").
+constexpr uint32_t kMaxHits = 32;
+constexpr uint32_t kMaxMismatch = 3;
+struct ApproxBatch {
+    const uint8_t *bytes;
+    const uint64_t *offs;
+    uint64_t npat;
+    uint32_t *out_nhits;
+    uint32_t *out_more;
+    uint32_t *out_mm;    // 1 word per slot: the hit's substitutions
+    uint32_t *out_subs;  // 6 words per slot: (position, symbol) x 3, by decreasing position
+    void *out_rng;       // 2 P-wide words per slot: lo, hi
+    uint64_t *tiles;     // null: intervals only
+    uint64_t max_occ;
+    uint32_t max_mm;
+    uint32_t max_hits;
+    uint32_t best;  // FMX_APPROX_BEST
+    uint32_t rev;
+    uint32_t stride;  // FMX_HINT_FIXED_LEN (0: read the offsets)
+};
+// k_approx, then (d_loc_offsets non-null) k_scan / k_emit over the slots'
+// records: d_tiles as for launch_locate of n * max_hits patterns.  In launch
+// order only.
+hipError_t launch_approx(const fmx_index *ix, const uint8_t *d_bytes, const uint64_t *d_offsets, uint64_t n,
+                         uint32_t flags, uint32_t max_mm, uint32_t max_hits, uint32_t mode, uint64_t max_occ,
+                         uint32_t *d_nhits, uint32_t *d_more, uint32_t *d_mm, uint32_t *d_subs, void *d_ranges,
+                         uint64_t *d_loc_offsets, void *d_locs, uint64_t cap, uint64_t *d_needed, uint64_t *d_tiles,
+                         uint64_t tiles_cap, uint32_t *status, hipStream_t stream);
 // `mid` (optional): an event recorded between k_search and k_emit (timing).
 // Fills grp's per-launch fields (first, emit_begin, the grouped fields) in place.
 hipError_t launch_locate_group(const fmx_index *ix, LocateGroup &grp, uint32_t stage_flags,
@@ -535,6 +565,9 @@ struct LayoutOps {
     // greedy seed chains (k_seeds): as match
     hipError_t (*seeds)(const QueryArgs &qa, uint32_t vb, uint32_t rec, const SeedBatch &sb, uint32_t wgs,
                         uint32_t stage, hipStream_t s);
+    // k-mismatch search (k_approx): as match
+    hipError_t (*approx)(const QueryArgs &qa, uint32_t vb, uint32_t rec, const ApproxBatch &ab, uint32_t wgs,
+                         uint32_t stage, hipStream_t s);
 };
 uint64_t locate_tiles_cap(uint64_t n);
 // Bytes per pattern of the search-result records in the locate workspace.

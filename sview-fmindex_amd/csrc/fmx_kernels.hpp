@@ -1,5 +1,5 @@
 // fmx_kernels.hpp — the query kernels that depend on the occ layout (P, N,
-// V, record size): k_count, k_search, k_match, k_seeds, k_emit, the deep-table level step, the
+// V, record size): k_count, k_search, k_match, k_seeds, k_approx, k_emit, the deep-table level step, the
 // full-SA walk and the record re-layout.  Instantiated per (P, N) in its own
 // translation unit (fmx_layout.hip, one object per layout, built in
 // parallel); launched through the LayoutOps table (fmx_internal.hpp).
@@ -521,6 +521,96 @@ __global__ __launch_bounds__(256, 8) void k_seeds(const QueryArgs a, const SeedB
         __syncthreads();
         const uint64_t tile = (uint64_t)blockIdx.x * ms + threadIdx.x;
         if (threadIdx.x < ms && tile < G) B.tiles[tile] = s_tile[threadIdx.x];
+    }
+}
+
+// ------------------------------------------------ k_approx (k-mismatch search)
+// One lane per pattern, k_seeds' shape, the pattern staged once: approx_search
+// hands the lane its pattern's variants in the contract's order, and the lane
+// stores the first max_hits of them — pattern i owns slots [i max_hits, (i+1)
+// max_hits): mm, the substitutions (3 pairs of position, symbol) and (lo, hi)
+// per slot, the unused pairs and slots zero — and ends the search at the
+// (max_hits + 1)-th (more = 1).  With B.tiles every slot also gets k_emit's
+// record — {lo, count, 0}, the count 0 unless the hit reports (count <=
+// max_occ; unused slots: zeros); one row under a full SA is located here by
+// that one read, any other is left to k_emit's walk (no sampled row is tracked
+// across the backtracking) — and the workgroup, whose slots are exactly
+// max_hits whole 256-slot tiles of k_emit, adds each reporting hit's count to
+// its tile's in LDS and writes the tile counts, as k_seeds does.
+template <typename P, int N, int VB, int REC>
+__global__ __launch_bounds__(256, 5) void k_approx(const QueryArgs a, const ApproxBatch B, uint32_t stage_bytes) {
+    __shared__ Tables<P> s;
+    FMX_DYN_LDS(s_pat);  // stage_bytes, then the k-mer table (dynamic)
+    __shared__ unsigned long long s_tile[kMaxHits];
+    stage_tables(a, s, s_pat + stage_bytes);
+    if (threadIdx.x < kMaxHits) s_tile[threadIdx.x] = 0;  // (visible after stage_patterns' barrier)
+    const uint8_t *__restrict__ bytes = B.bytes;
+    const uint64_t npat = B.npat, first = (uint64_t)blockIdx.x * 256u;
+    const bool rev = B.rev != 0;
+    uint64_t beg, end, b0, b1;
+    const bool staged =
+        stage_patterns(s, s_pat, bytes, B.offs, npat, first, rev, stage_bytes, B.stride, a.status, beg, end, b0, b1);
+    __syncthreads();
+    const uint64_t i = first + threadIdx.x;
+    const uint32_t mh = B.max_hits;
+    const bool loc = B.tiles != nullptr;         // (workgroup-uniform)
+    const uint64_t G = (npat * mh + 255) / 256;  // the batch's 256-slot tiles
+    if (i < npat) {
+        const PatView pv = pattern_view(s, s_pat, staged, bytes, beg, end, b0, b1, rev);
+        // the outputs are addressed from the workgroup's first slot (uniform) by a 32-bit slot number
+        const uint64_t slot0 = first * mh;
+        uint32_t *__restrict__ mm = B.out_mm + slot0;
+        uint32_t *__restrict__ subs = B.out_subs + 6 * slot0;
+        P *__restrict__ rng = reinterpret_cast<P *>(B.out_rng) + 2 * slot0;
+        SearchRec<P> *__restrict__ recs = nullptr;
+        if (loc) recs = reinterpret_cast<SearchRec<P> *>(B.tiles + 2 * G) + slot0;
+        uint32_t ls = threadIdx.x * mh;  // hit j's slot in the workgroup: tile ls >> 8 of its max_hits
+        const uint32_t ls_end = ls + mh;
+        uint32_t more = 0;
+        approx_search<P, N, VB, REC>(
+            a, s, pv, B.max_mm, B.best != 0,
+            [&](uint32_t d, P lo, P hi, const ApproxFrame<P> &f0, const ApproxFrame<P> &f1, const ApproxFrame<P> &f2) {
+                if (ls == ls_end) {
+                    more = 1;
+                    return true;
+                }
+                mm[ls] = d;
+                uint32_t *__restrict__ sb = subs + 6 * ls;
+                sb[0] = d > 0 ? f0.pos : 0u;
+                sb[1] = d > 0 ? f0.sym() : 0u;
+                sb[2] = d > 1 ? f1.pos : 0u;
+                sb[3] = d > 1 ? f1.sym() : 0u;
+                sb[4] = d > 2 ? f2.pos : 0u;
+                sb[5] = d > 2 ? f2.sym() : 0u;
+                rng[2 * ls] = lo;
+                rng[2 * ls + 1] = hi;
+                if (loc) {
+                    const uint64_t cnt = (uint64_t)(hi - lo) <= B.max_occ ? (uint64_t)(hi - lo) : 0;
+                    if (cnt == 1 && a.safull != nullptr)  // (walk_row's one read)
+                        recs[ls] = SearchRec<P>{reinterpret_cast<const P *>(a.safull)[(uint64_t)lo * a.sa_stride], P(1),
+                                                1ull};
+                    else
+                        recs[ls] = SearchRec<P>{lo, (P)cnt, 0ull};
+                    if (cnt) atomicAdd(&s_tile[ls >> 8], (unsigned long long)cnt);
+                }
+                ++ls;
+                return false;
+            });
+        (B.out_nhits + first)[threadIdx.x] = mh - (ls_end - ls);  // (uniform base + lane: i need not stay live)
+        (B.out_more + first)[threadIdx.x] = more;
+        for (; ls < ls_end; ++ls) {
+            mm[ls] = 0;
+            uint32_t *__restrict__ sb = subs + 6 * ls;
+#pragma unroll
+            for (int u = 0; u < 6; ++u) sb[u] = 0;
+            rng[2 * ls] = rng[2 * ls + 1] = 0;
+            if (loc) recs[ls] = SearchRec<P>{P(0), P(0), 0ull};
+        }
+    }
+    if (loc) {
+        __syncthreads();
+        const uint64_t tile = (uint64_t)blockIdx.x * mh + threadIdx.x;
+        if (threadIdx.x < mh && tile < G) B.tiles[tile] = s_tile[threadIdx.x];
     }
 }
 

@@ -195,6 +195,14 @@ hipError_t disp(uint32_t vb, uint32_t rec, F &&f) {
     });
 }
 
+[[maybe_unused]] hipError_t op_approx(const QueryArgs &qa, uint32_t vb, uint32_t rec, const ApproxBatch &ab, uint32_t wgs,
+                                      uint32_t stage, hipStream_t s) {
+    return disp(vb, rec, [&]<int VB, int R>() {
+        hipLaunchKernelGGL((k_approx<P, N, VB, R>), dim3(wgs), dim3(256), stage + qa.kt_lds_bytes, s, qa, ab, stage);
+        return hipGetLastError();
+    });
+}
+
 }  // namespace
 
 #if !defined(__HIP_DEVICE_COMPILE__)  // a host table (the device pass only instantiates the kernels)
@@ -203,7 +211,8 @@ hipError_t disp(uint32_t vb, uint32_t rec, F &&f) {
 extern const LayoutOps FMX_OPS_NAME(FMX_LAYOUT_P, FMX_LAYOUT_N, FMX_LAYOUT_VB);
 const LayoutOps FMX_OPS_NAME(FMX_LAYOUT_P, FMX_LAYOUT_N, FMX_LAYOUT_VB) = {op_count, op_search, op_emit, op_search_grouped,
                                                            op_dlut_level, op_full_sa, op_relayout, op_locate,
-                                                           op_emit_chain, op_match, op_seeds};
+                                                           op_emit_chain, op_match, op_seeds,
+                                                           op_approx};
 #endif
 
 }  // namespace fmx

@@ -18,6 +18,8 @@
 //   k_seeds   : greedy seed chains: k_match's search restarted on ever
 //               shorter prefixes of the staged pattern, a slot per seed;
 //               then k_scan / k_emit over the slots
+//   k_approx  : k-mismatch search: a bounded backtracking walk per lane over
+//               the staged pattern, a slot per hit; then k_scan / k_emit
 //   k_scan    : tile offsets of batches too large for k_emit's own sum
 //   k_emit    : output offsets, then every location: settled ones copied,
 //               the rows of multi-row intervals walked, dealt across the 64
@@ -733,6 +735,38 @@ hipError_t launch_seeds(const fmx_index *ix, const uint8_t *d_bytes, const uint6
                        max_occ, max_seeds, min_len, skip,     rev,    stride};
     const Disp d = dispatch(ix);
     hipError_t e = d.ops->seeds(qa, d.vb, d.rec, sb, (uint32_t)wgs, stage_bytes_for(flags), stream);
+    if (e != hipSuccess || !loc) return e;
+    // one batch of `slots` records in launch order for k_scan / k_emit (neither reads the patterns)
+    LocateGroup grp;
+    group_reset(grp);
+    grp.tile_begin[0] = 0;
+    grp.b[0] = LocateBatch{nullptr, nullptr, slots, nullptr, d_loc_offsets, d_locs, cap, d_needed, d_tiles, 0u, 0u};
+    grp.n = 1;
+    return launch_emit(ix, qa, grp, (uint32_t)tiles, 0u, stream);
+}
+
+// k-mismatch search, in launch order: k_approx (a workgroup per 256 patterns),
+// then — when locations are asked for — the locate's own last kernels over the
+// n * max_hits slots' records, one "pattern" per slot (as launch_seeds).
+hipError_t launch_approx(const fmx_index *ix, const uint8_t *d_bytes, const uint64_t *d_offsets, uint64_t n,
+                         uint32_t flags, uint32_t max_mm, uint32_t max_hits, uint32_t mode, uint64_t max_occ,
+                         uint32_t *d_nhits, uint32_t *d_more, uint32_t *d_mm, uint32_t *d_subs, void *d_ranges,
+                         uint64_t *d_loc_offsets, void *d_locs, uint64_t cap, uint64_t *d_needed, uint64_t *d_tiles,
+                         uint64_t tiles_cap, uint32_t *status, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    if (max_mm > kMaxMismatch || max_hits == 0 || max_hits > kMaxHits || n > ~0ull / max_hits)
+        return hipErrorInvalidValue;
+    QueryArgs qa = ix->qa;
+    qa.status = status;
+    const uint64_t slots = n * max_hits, tiles = (slots + 255) / 256, wgs = (n + 255) / 256;
+    const bool loc = d_loc_offsets != nullptr;
+    if (tiles > 0x7FFFFFFFull || (loc && (tiles > tiles_cap || !d_tiles))) return hipErrorInvalidValue;
+    const uint32_t rev = (flags & FMX_PATTERN_REVERSED) ? 1u : 0u, stride = flags >> 16;
+    const ApproxBatch ab{d_bytes, d_offsets, n,      d_nhits, d_more,   d_mm,
+                         d_subs,  d_ranges,  loc ? d_tiles : nullptr,  max_occ, max_mm, max_hits,
+                         (mode & FMX_APPROX_BEST) ? 1u : 0u, rev, stride};
+    const Disp d = dispatch(ix);
+    hipError_t e = d.ops->approx(qa, d.vb, d.rec, ab, (uint32_t)wgs, stage_bytes_for(flags), stream);
     if (e != hipSuccess || !loc) return e;
     // one batch of `slots` records in launch order for k_scan / k_emit (neither reads the patterns)
     LocateGroup grp;

@@ -1,0 +1,98 @@
+"""Guard bands around fmx_approx_batch_async: the one run that the emulator
+tests (test_approx_guard_simt.py) and the GPU tests (test_gpu_approx_guard.py)
+share.  The arena, its fill bytes and the two memories are _guard_cases.py's,
+the batches and expected values _approx_cases.py's.
+
+Every buffer of the call is carved at its exact size and weakest alignment
+(d_nhits, d_more, d_mm and d_subs 4 B past a 16-B boundary, d_ranges and d_locs
+P bytes, the uint64 arrays 8, the workspace — fmx_locate_workspace_size(n *
+max_hits) bytes — 16 B past a 256-B boundary, the pattern bytes at the given
+skew, flush against the end guard).  After the launch: every guard byte
+intact, the inputs unchanged, every output the expected value,
+d_locs[min(cap, total):cap] still the prefill.  Batches of 257 and 700
+patterns run once more with a 1 KB stage: the unstaged path of k_approx."""
+import numpy as np
+
+from _approx_cases import batch, expected_arrays
+from _guard_cases import FILL_OUT, Arena
+
+MAX_MM, MAX_HITS, MAX_OCC = 2, 3, 3
+BATCH_SIZES = (1, 257, 700)
+SKEWS = (0, 1, 7, 15)
+CAPS = ("total", "total-1", "zero-null")
+# (P bytes, planes, vector bits): u32 and u64 positions
+LAYOUTS = [(4, 3, 64), (8, 5, 128)]
+
+
+def run_approx(pkg, ix, mem_cls, case, orc, pb, n, cap_name, skew, reversed, locate=True, stage_kb=0, best=False):
+    """stage_kb: FMX_HINT_STAGE_KB; 1 leaves no full tile of these batches room
+    in LDS, so k_approx reads every pattern from HBM."""
+    pats = batch(case, n, MAX_MM)
+    mh = MAX_HITS
+    exp = expected_arrays(case, orc, pats, MAX_MM, mh, best, MAX_OCC)
+    total = int(exp[5][-1])
+    if n >= 256:
+        cnt = np.diff(exp[5].astype(np.int64))
+        stored = exp[4][:, :, 1].reshape(-1) > 0
+        assert total > n // 2 and (cnt[stored] == 0).sum() >= 4 and (~stored).sum() >= 100, "every slot reports"
+    cap = {"total": total, "total-1": total - 1, "zero-null": 0}[cap_name] if locate else 0
+    if cap < 0:
+        return  # (a batch with no location has no cap below its total)
+    what = f"approx n={n} cap={cap_name}({cap}) skew={skew} rev={reversed} locate={locate} stage_kb={stage_kb}"
+    if stage_kb:
+        tile_bytes = [sum(len(p) for p in pats[t:t + 256]) for t in range(0, n, 256)]
+        # (every full tile; the one-pattern last tile of a 257-pattern batch still fits)
+        assert min(tile_bytes[:n // 256]) > 1024 * stage_kb, "a full tile fits the stage: not the unstaged path"
+    P = np.uint32 if pb == 4 else np.uint64
+    q = [p[::-1] for p in pats] if reversed else pats
+    data, offsets = pkg.pack_patterns(q)
+    arena = Arena(mem_cls)
+    c = arena.carve
+    S = n * mh
+    if locate:
+        wsb = ix.locate_workspace_size(S)
+        c("ws", wsb, 16, 16, boundary=256)
+    c("offsets", 8 * (n + 1), 8, 8, data=offsets)
+    if locate:
+        c("loc_offsets", 8 * (S + 1), 8, 8)
+        c("needed", 8, 8, 8)
+        if cap:
+            # guard bytes for every location past cap: an emit that ignored cap stays inside the arena
+            c("locs", pb * cap, pb, pb, tail=pb * max(total - cap, 0))
+    c("nhits", 4 * n, 4, 4)
+    c("more", 4 * n, 4, 4)
+    c("mm", 4 * S, 4, 4)
+    c("subs", 24 * S, 4, 4)
+    c("ranges", 2 * pb * S, pb, pb)
+    c("bytes", data.size, 1, skew, data=data)
+    arena.commit()
+    off, nb = arena.bufs["bytes"]
+    assert off + nb == arena.size - 4096, "the last pattern byte is not the byte before the end guard"
+    p = arena.ptr
+    assert p("bytes") % 16 == skew and p("ranges") % 16 == pb % 16
+    assert all(p(x) % 16 == 4 for x in ("nhits", "more", "mm", "subs"))
+    kw = dict(max_mm=MAX_MM, max_hits=mh, best=best, max_occ=MAX_OCC, reversed=reversed, stage_kb=stage_kb)
+    outs = (p("nhits"), p("more"), p("mm"), p("subs"), p("ranges"))
+    if locate:
+        assert p("ws") % 256 == 16
+        ix.approx_batch_async(p("bytes"), p("offsets"), n, *outs, p("loc_offsets"), p("locs"), cap, p("needed"),
+                              p("ws"), wsb, **kw)
+    else:
+        ix.approx_batch_async(p("bytes"), p("offsets"), n, *outs, **kw)
+    ix.sync()
+    arena.image()
+    arena.check_guards_and_inputs(what)
+    v = arena.view
+    assert np.array_equal(v("nhits", np.uint32), exp[0]), f"{what}: d_nhits"
+    assert np.array_equal(v("more", np.uint32), exp[1]), f"{what}: d_more"
+    assert np.array_equal(v("mm", np.uint32).reshape(n, mh), exp[2]), f"{what}: d_mm"
+    assert np.array_equal(v("subs", np.uint32).reshape(n, mh, 3, 2), exp[3]), f"{what}: d_subs"
+    assert np.array_equal(v("ranges", P).reshape(n, mh, 2).astype(np.int64), exp[4]), f"{what}: d_ranges"
+    if not locate:
+        return
+    assert np.array_equal(v("loc_offsets", np.uint64), exp[5]), f"{what}: d_loc_offsets"
+    assert int(v("needed", np.uint64)[0]) == total, f"{what}: *d_needed"
+    if cap:
+        k = min(cap, total)
+        assert np.array_equal(v("locs", P)[:k].astype(np.uint64), exp[6][:k]), f"{what}: d_locs[:min(cap, total)]"
+        assert (v("locs", np.uint8)[k * pb:] == FILL_OUT).all(), f"{what}: d_locs written past min(cap, total)"

@@ -1,0 +1,59 @@
+"""Guard bands around fmx_approx_batch_async on the CPU: the engine's own
+sources under the SIMT shim (tests/simt), every buffer of the call carved at
+its exact size and weakest alignment out of one 0xA5-filled array
+(_approx_guard_cases.py, on the arena of _guard_cases.py), pattern-byte skews
+0, 1, 7 and 15, batches of 1, 257 and 700 patterns at max_mm = 2 and max_hits =
+3, caps total, total - 1 and 0 with d_locs = NULL, intervals only (no
+workspace, no location buffers), and the unstaged path (a 1 KB stage): guards
+and inputs untouched, every output the expected value,
+d_locs[min(cap, total):cap] unwritten."""
+import ctypes as C
+import os
+import subprocess
+
+import pytest
+
+import _approx_guard_cases as AG
+from _approx_cases import case_for, open_index
+from _guard_cases import HostMem
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+SIMT_DIR = os.path.join(HERE, "simt")
+SIMT_LIB = os.path.join(SIMT_DIR, "libfmx_simt.so")
+
+
+@pytest.fixture(scope="module")
+def simt(pkg):
+    subprocess.check_call(["make", "-s", "-j", str(min(8, os.cpu_count() or 1)), "-C", SIMT_DIR])
+    n = pkg._native
+    L = C.CDLL(SIMT_LIB)
+    for name, (res, args) in n.SIGNATURES.items():
+        f = getattr(L, name)
+        f.restype = res
+        f.argtypes = args
+    L.simt_config.argtypes = [C.c_uint64, C.c_double]
+    L.simt_config.restype = None
+    L.simt_defer.argtypes = [C.c_int, C.c_double]
+    L.simt_defer.restype = None
+    # deferred streams, as tests/test_simt.py: queued work runs at a random later host call
+    L.simt_defer(1, 0.25)
+    saved = n._lib
+    n._lib = L
+    yield L
+    n._lib = saved
+
+
+@pytest.mark.parametrize("skew", AG.SKEWS)
+@pytest.mark.parametrize("pb,planes,vb", AG.LAYOUTS)
+def test_approx_guard_simt(pkg, O, simt, pb, planes, vb, skew):
+    simt.simt_config(9900 + pb + planes + skew, 0.5)
+    case = case_for(planes)
+    ix, orc = open_index(pkg, O, case, pb, planes, vb, 1)
+    for j, n in enumerate(AG.BATCH_SIZES):
+        for ci, cap in enumerate(AG.CAPS):
+            AG.run_approx(pkg, ix, HostMem, case, orc, pb, n, cap, skew, (j + ci + skew) % 2 == 1, best=ci == 1)
+        AG.run_approx(pkg, ix, HostMem, case, orc, pb, n, None, skew, (j + skew) % 2 == 0, locate=False)
+        if n > 256:  # the patterns read from HBM (no tile fits a 1 KB stage), both directions
+            for rev in (False, True):
+                AG.run_approx(pkg, ix, HostMem, case, orc, pb, n, "total", skew, rev, stage_kb=1)
+    ix.close()
