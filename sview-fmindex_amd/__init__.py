@@ -345,6 +345,43 @@ def _ptr(a: Optional[np.ndarray]):
     return None if a is None else C.c_void_p(a.ctypes.data)
 
 
+def _vp(x: int):
+    """An optional device pointer (or stream) of the async calls: 0 = NULL."""
+    return C.c_void_p(x) if x else None
+
+
+def _host_query(name: str, h, dt, patterns, reversed: bool, params: Optional[tuple] = None,
+                max_occ: Optional[int] = None, outs=lambda n: (), per: int = 1, locate: bool = True,
+                cap: int = 1 << 16):
+    """One host-buffer query `name(h, bytes, offsets, n, flags, *params,
+    max_occ, *outs(n), loc_offsets, locations, cap, &needed)` (params None: a
+    call without them and without max_occ): the patterns packed, max_occ None
+    as no bound, and — with `locate` — the locations of n * per slots, their
+    buffer grown to `needed` and the call repeated once on FMX_E_CAPACITY.
+    Returns (n, outputs, loc_offsets uint64[n * per + 1], locations[:needed]),
+    the last two None without `locate`."""
+    data, offsets = patterns if isinstance(patterns, tuple) else pack_patterns(patterns)
+    n = offsets.size - 1
+    out = outs(n)
+    flags = _n.FMX_PATTERN_REVERSED if reversed else 0
+    mid = () if params is None else params + ((1 << 64) - 1 if max_occ is None else int(max_occ),)
+    head = (h, _ptr(data) if data.size else None, _ptr(offsets), n, flags) + mid + tuple(_ptr(o) for o in out)
+    fn = getattr(_n.lib(), name)
+    needed = C.c_uint64()
+    if not locate:
+        _check(fn(*head, None, None, 0, C.byref(needed)), name)
+        return n, out, None, None
+    loc_off = np.zeros(n * max(per, 0) + 1, dtype=np.uint64)
+    locs = np.zeros(max(cap, 1), dtype=dt)
+    st = fn(*head, _ptr(loc_off), _ptr(locs), cap, C.byref(needed))
+    if st == _n.FMX_E_CAPACITY:  # (the first guess was short: once more with room for every location)
+        cap = needed.value
+        locs = np.zeros(max(cap, 1), dtype=dt)
+        st = fn(*head, _ptr(loc_off), _ptr(locs), cap, C.byref(needed))
+    _check(st, name)
+    return n, out, loc_off, locs[:needed.value]
+
+
 # ----------------------------------------------------------------- FmIndex
 
 class FmIndex:
@@ -530,24 +567,8 @@ class FmIndex:
         """Locations of many patterns: (offsets uint64[n+1], locations P[total]);
         pattern i's locations are locations[offsets[i]:offsets[i+1]] in
         suffix-array-row order."""
-        data, offsets = patterns if isinstance(patterns, tuple) else pack_patterns(patterns)
-        n = offsets.size - 1
-        loc_off = np.zeros(n + 1, dtype=np.uint64)
-        flags = _n.FMX_PATTERN_REVERSED if reversed else 0
-        needed = C.c_uint64()
-        if cap is None:
-            # size the output from the counts (second call only if they do not fit)
-            cap = 1 << 16
-        locs = np.zeros(max(cap, 1), dtype=self._dt)
-        st = _n.lib().fmx_locate_batch(self._h, _ptr(data) if data.size else None, _ptr(offsets), n, flags,
-                                       _ptr(loc_off), _ptr(locs), cap, C.byref(needed))
-        if st == _n.FMX_E_CAPACITY:
-            cap = needed.value
-            locs = np.zeros(max(cap, 1), dtype=self._dt)
-            st = _n.lib().fmx_locate_batch(self._h, _ptr(data) if data.size else None, _ptr(offsets), n, flags,
-                                           _ptr(loc_off), _ptr(locs), cap, C.byref(needed))
-        _check(st, "fmx_locate_batch")
-        return loc_off, locs[:needed.value]
+        return _host_query("fmx_locate_batch", self._h, self._dt, patterns, reversed,
+                           cap=(1 << 16) if cap is None else cap)[2:]
 
     # -- longest-suffix match (greedy backward seeding) ---------------------
     def match(self, pattern: bytes) -> Tuple[int, int, int]:
@@ -566,30 +587,10 @@ class FmIndex:
         interval, always the true values; locations (suffix-array-row order)
         are emitted only for patterns with lens[i] >= max(min_len, 1) and
         hi - lo <= max_occ (None: no bound)."""
-        data, offsets = patterns if isinstance(patterns, tuple) else pack_patterns(patterns)
-        n = offsets.size - 1
-        lens = np.zeros(max(n, 1), dtype=np.uint32)
-        rng = np.zeros((max(n, 1), 2), dtype=self._dt)
-        flags = _n.FMX_PATTERN_REVERSED if reversed else 0
-        occ = (1 << 64) - 1 if max_occ is None else int(max_occ)
-        needed = C.c_uint64()
-        if not locate:
-            _check(_n.lib().fmx_match_batch(self._h, _ptr(data) if data.size else None, _ptr(offsets), n, flags,
-                                            int(min_len), occ, _ptr(lens), _ptr(rng), None, None, 0,
-                                            C.byref(needed)), "fmx_match_batch")
-            return lens[:n], rng[:n]
-        loc_off = np.zeros(n + 1, dtype=np.uint64)
-        cap = 1 << 16
-        locs = np.zeros(cap, dtype=self._dt)
-        args = lambda: (self._h, _ptr(data) if data.size else None, _ptr(offsets), n, flags, int(min_len), occ,  # noqa
-                        _ptr(lens), _ptr(rng), _ptr(loc_off), _ptr(locs), cap, C.byref(needed))
-        st = _n.lib().fmx_match_batch(*args())
-        if st == _n.FMX_E_CAPACITY:
-            cap = needed.value
-            locs = np.zeros(max(cap, 1), dtype=self._dt)
-            st = _n.lib().fmx_match_batch(*args())
-        _check(st, "fmx_match_batch")
-        return lens[:n], rng[:n], loc_off, locs[:needed.value]
+        outs = lambda n: (np.zeros(max(n, 1), dtype=np.uint32), np.zeros((max(n, 1), 2), dtype=self._dt))  # noqa: E731
+        n, (lens, rng), loff, locs = _host_query("fmx_match_batch", self._h, self._dt, patterns, reversed,
+                                                 (int(min_len),), max_occ, outs, locate=locate)
+        return (lens[:n], rng[:n]) + ((loff, locs) if locate else ())
 
     # -- greedy seed chains (the match restarted until the pattern is used up) --
     def seeds(self, pattern: bytes, max_seeds: int = 8, min_len: int = 1, skip: int = 0,
@@ -613,33 +614,17 @@ class FmIndex:
         0 or max_seeds are stored; rest[i] = the e left (0: all parsed); unused
         slots are zero.  Slot i * max_seeds + j holds the seed's locations
         (suffix-array-row order) when hi - lo <= max_occ (None: no bound)."""
-        data, offsets = patterns if isinstance(patterns, tuple) else pack_patterns(patterns)
-        n, ms = offsets.size - 1, int(max_seeds)
-        rows = max(n, 1) * max(ms, 1)
-        ns = np.zeros(max(n, 1), dtype=np.uint32)
-        rest = np.zeros(max(n, 1), dtype=np.uint32)
-        spans = np.zeros((rows, 2), dtype=np.uint32)
-        rng = np.zeros((rows, 2), dtype=self._dt)
-        flags = _n.FMX_PATTERN_REVERSED if reversed else 0
-        occ = (1 << 64) - 1 if max_occ is None else int(max_occ)
-        needed = C.c_uint64()
-        shaped = lambda: (ns[:n], rest[:n], spans[:n * ms].reshape(n, ms, 2),  # noqa: E731
-                          rng[:n * ms].reshape(n, ms, 2))
-        head = (self._h, _ptr(data) if data.size else None, _ptr(offsets), n, flags, ms, int(min_len), int(skip), occ,
-                _ptr(ns), _ptr(rest), _ptr(spans), _ptr(rng))
-        if not locate:
-            _check(_n.lib().fmx_seeds_batch(*head, None, None, 0, C.byref(needed)), "fmx_seeds_batch")
-            return shaped()
-        loc_off = np.zeros(n * max(ms, 0) + 1, dtype=np.uint64)
-        cap = 1 << 16
-        locs = np.zeros(cap, dtype=self._dt)
-        st = _n.lib().fmx_seeds_batch(*head, _ptr(loc_off), _ptr(locs), cap, C.byref(needed))
-        if st == _n.FMX_E_CAPACITY:
-            cap = needed.value
-            locs = np.zeros(max(cap, 1), dtype=self._dt)
-            st = _n.lib().fmx_seeds_batch(*head, _ptr(loc_off), _ptr(locs), cap, C.byref(needed))
-        _check(st, "fmx_seeds_batch")
-        return shaped() + (loc_off, locs[:needed.value])
+        ms = int(max_seeds)
+
+        def outs(n):
+            rows = max(n, 1) * max(ms, 1)
+            return (np.zeros(max(n, 1), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.uint32),
+                    np.zeros((rows, 2), dtype=np.uint32), np.zeros((rows, 2), dtype=self._dt))
+
+        n, (ns, rest, spans, rng), loff, locs = _host_query("fmx_seeds_batch", self._h, self._dt, patterns, reversed,
+                                                            (ms, int(min_len), int(skip)), max_occ, outs, ms, locate)
+        return ((ns[:n], rest[:n], spans[:n * ms].reshape(n, ms, 2), rng[:n * ms].reshape(n, ms, 2))
+                + ((loff, locs) if locate else ()))
 
     # -- k-mismatch search (substitutions only, a bounded backtracking walk on the device) --
     def approx(self, pattern: bytes, max_mm: int = 1, max_hits: int = 8,
@@ -668,35 +653,19 @@ class FmIndex:
         unused entries are zero.  Slot i * max_hits + j holds the variant's
         locations (suffix-array-row order) when hi - lo <= max_occ (None: no
         bound)."""
-        data, offsets = patterns if isinstance(patterns, tuple) else pack_patterns(patterns)
-        n, mh = offsets.size - 1, int(max_hits)
-        rows = max(n, 1) * max(mh, 1)
-        nh = np.zeros(max(n, 1), dtype=np.uint32)
-        more = np.zeros(max(n, 1), dtype=np.uint32)
-        mm = np.zeros(rows, dtype=np.uint32)
-        subs = np.zeros((rows, 6), dtype=np.uint32)
-        rng = np.zeros((rows, 2), dtype=self._dt)
-        flags = _n.FMX_PATTERN_REVERSED if reversed else 0
-        mode = _n.FMX_APPROX_BEST if best else 0
-        occ = (1 << 64) - 1 if max_occ is None else int(max_occ)
-        needed = C.c_uint64()
-        shaped = lambda: (nh[:n], more[:n], mm[:n * mh].reshape(n, mh),  # noqa: E731
-                          subs[:n * mh].reshape(n, mh, 3, 2), rng[:n * mh].reshape(n, mh, 2))
-        head = (self._h, _ptr(data) if data.size else None, _ptr(offsets), n, flags, int(max_mm), mh, mode, occ,
-                _ptr(nh), _ptr(more), _ptr(mm), _ptr(subs), _ptr(rng))
-        if not locate:
-            _check(_n.lib().fmx_approx_batch(*head, None, None, 0, C.byref(needed)), "fmx_approx_batch")
-            return shaped()
-        loc_off = np.zeros(n * max(mh, 0) + 1, dtype=np.uint64)
-        cap = 1 << 16
-        locs = np.zeros(cap, dtype=self._dt)
-        st = _n.lib().fmx_approx_batch(*head, _ptr(loc_off), _ptr(locs), cap, C.byref(needed))
-        if st == _n.FMX_E_CAPACITY:
-            cap = needed.value
-            locs = np.zeros(max(cap, 1), dtype=self._dt)
-            st = _n.lib().fmx_approx_batch(*head, _ptr(loc_off), _ptr(locs), cap, C.byref(needed))
-        _check(st, "fmx_approx_batch")
-        return shaped() + (loc_off, locs[:needed.value])
+        mh = int(max_hits)
+
+        def outs(n):
+            rows = max(n, 1) * max(mh, 1)
+            return (np.zeros(max(n, 1), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.uint32),
+                    np.zeros(rows, dtype=np.uint32), np.zeros((rows, 6), dtype=np.uint32),
+                    np.zeros((rows, 2), dtype=self._dt))
+
+        params = (int(max_mm), mh, _n.FMX_APPROX_BEST if best else 0)
+        n, (nh, more, mm, subs, rng), loff, locs = _host_query("fmx_approx_batch", self._h, self._dt, patterns,
+                                                               reversed, params, max_occ, outs, mh, locate)
+        return ((nh[:n], more[:n], mm[:n * mh].reshape(n, mh), subs[:n * mh].reshape(n, mh, 3, 2),
+                 rng[:n * mh].reshape(n, mh, 2)) + ((loff, locs) if locate else ()))
 
     # -- device-resident API (pointers are ints; stream is a hipStream_t) --
     def count_batch_async(self, d_bytes: int, d_offsets: int, n: int, d_counts: int,
@@ -735,11 +704,10 @@ class FmIndex:
         workspace of locate_workspace_size(n) bytes; d_loc_offsets = 0:
         lengths and intervals only, no workspace."""
         flags = _flags(reversed, long_patterns, stage_kb, fixed_len)
-        v = lambda x: C.c_void_p(x) if x else None  # noqa: E731
         _check(_n.lib().fmx_match_batch_async(
             self._h, C.c_void_p(d_bytes), C.c_void_p(d_offsets), n, flags, int(min_len),
             (1 << 64) - 1 if max_occ is None else int(max_occ), C.c_void_p(d_lens), C.c_void_p(d_ranges),
-            v(d_loc_offsets), v(d_locs), cap, v(d_needed), v(d_ws), ws_bytes, v(stream)))
+            _vp(d_loc_offsets), _vp(d_locs), cap, _vp(d_needed), _vp(d_ws), ws_bytes, _vp(stream)))
 
     def seeds_batch_async(self, d_bytes: int, d_offsets: int, n: int, d_nseeds: int, d_rest: int, d_spans: int,
                           d_ranges: int, d_loc_offsets: int = 0, d_locs: int = 0, cap: int = 0, d_needed: int = 0,
@@ -753,11 +721,10 @@ class FmIndex:
         locate_workspace_size(n * max_seeds) bytes; d_loc_offsets = 0: spans
         and intervals only, no workspace."""
         flags = _flags(reversed, long_patterns, stage_kb, fixed_len)
-        v = lambda x: C.c_void_p(x) if x else None  # noqa: E731
         _check(_n.lib().fmx_seeds_batch_async(
             self._h, C.c_void_p(d_bytes), C.c_void_p(d_offsets), n, flags, int(max_seeds), int(min_len), int(skip),
-            (1 << 64) - 1 if max_occ is None else int(max_occ), v(d_nseeds), v(d_rest), v(d_spans), v(d_ranges),
-            v(d_loc_offsets), v(d_locs), cap, v(d_needed), v(d_ws), ws_bytes, v(stream)))
+            (1 << 64) - 1 if max_occ is None else int(max_occ), _vp(d_nseeds), _vp(d_rest), _vp(d_spans), _vp(d_ranges),
+            _vp(d_loc_offsets), _vp(d_locs), cap, _vp(d_needed), _vp(d_ws), ws_bytes, _vp(stream)))
 
     def approx_batch_async(self, d_bytes: int, d_offsets: int, n: int, d_nhits: int, d_more: int, d_mm: int,
                            d_subs: int, d_ranges: int, d_loc_offsets: int = 0, d_locs: int = 0, cap: int = 0,
@@ -771,12 +738,11 @@ class FmIndex:
         over a workspace of locate_workspace_size(n * max_hits) bytes;
         d_loc_offsets = 0: intervals only, no workspace."""
         flags = _flags(reversed, long_patterns, stage_kb, fixed_len)
-        v = lambda x: C.c_void_p(x) if x else None  # noqa: E731
         _check(_n.lib().fmx_approx_batch_async(
             self._h, C.c_void_p(d_bytes), C.c_void_p(d_offsets), n, flags, int(max_mm), int(max_hits),
-            _n.FMX_APPROX_BEST if best else 0, (1 << 64) - 1 if max_occ is None else int(max_occ), v(d_nhits),
-            v(d_more), v(d_mm), v(d_subs), v(d_ranges), v(d_loc_offsets), v(d_locs), cap, v(d_needed), v(d_ws),
-            ws_bytes, v(stream)))
+            _n.FMX_APPROX_BEST if best else 0, (1 << 64) - 1 if max_occ is None else int(max_occ), _vp(d_nhits),
+            _vp(d_more), _vp(d_mm), _vp(d_subs), _vp(d_ranges), _vp(d_loc_offsets), _vp(d_locs), cap, _vp(d_needed),
+            _vp(d_ws), ws_bytes, _vp(stream)))
 
     @staticmethod
     def locate_job(d_bytes: int, d_offsets: int, n: int, d_loc_offsets: int, d_locs: int, cap: int,
@@ -883,22 +849,8 @@ class MultiDeviceIndex:
 
     def locate_batch(self, patterns, reversed: bool = False,
                      cap: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
-        data, offsets = patterns if isinstance(patterns, tuple) else pack_patterns(patterns)
-        n = offsets.size - 1
-        loc_off = np.zeros(n + 1, dtype=np.uint64)
-        flags = _n.FMX_PATTERN_REVERSED if reversed else 0
-        needed = C.c_uint64()
-        cap = (1 << 16) if cap is None else cap
-        locs = np.zeros(max(cap, 1), dtype=self._dt)
-        args = lambda: (self._h, _ptr(data) if data.size else None, _ptr(offsets), n, flags, _ptr(loc_off),  # noqa
-                        _ptr(locs), cap, C.byref(needed))
-        st = _n.lib().fmx_multi_locate_batch(*args())
-        if st == _n.FMX_E_CAPACITY:
-            cap = needed.value
-            locs = np.zeros(max(cap, 1), dtype=self._dt)
-            st = _n.lib().fmx_multi_locate_batch(*args())
-        _check(st, "fmx_multi_locate_batch")
-        return loc_off, locs[:needed.value]
+        return _host_query("fmx_multi_locate_batch", self._h, self._dt, patterns, reversed,
+                           cap=(1 << 16) if cap is None else cap)[2:]
 
 
 # ---------------------------------------------------------- FmIndexBuilder

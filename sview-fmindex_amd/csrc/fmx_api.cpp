@@ -1191,19 +1191,25 @@ fmx_status fmx_workspace_bytes(uint64_t n, uint32_t pos_bytes, uint64_t *bytes) 
     return FMX_OK;
 }
 
+// A workspace the launches take at all: room for the header, 16-B aligned (the grouped passes' 16-B vectors: fmx.h)
+static bool ws_ok(const void *d_ws, uint64_t ws_bytes) {
+    return d_ws && ws_bytes >= kWsHeader + 16 && ((uintptr_t)d_ws & 15) == 0;
+}
+
+// An empty batch's location outputs: one zero offset, a zero total.
+static hipError_t zero_locs(uint64_t *d_loc_offsets, uint64_t *d_needed, hipStream_t s) {
+    const hipError_t e = hipMemsetAsync(d_loc_offsets, 0, 8, s);
+    return e == hipSuccess ? hipMemsetAsync(d_needed, 0, 8, s) : e;
+}
+
 fmx_status fmx_locate_batch_async(fmx_index *ix, const uint8_t *d_bytes, const uint64_t *d_offsets, uint64_t n,
                                   uint32_t flags, void *d_counts, uint64_t *d_loc_offsets, void *d_locs,
                                   uint64_t cap, uint64_t *d_needed, void *d_ws, uint64_t ws_bytes, void *stream) {
     if (!ix || !d_loc_offsets || !d_needed || (n && (!d_bytes || !d_offsets)) || (cap && !d_locs)) return FMX_E_ARG;
-    if (!d_ws || ws_bytes < kWsHeader + 16) return FMX_E_ARG;
-    if (((uintptr_t)d_ws & 15) != 0) return FMX_E_ARG;  // (the grouped passes' 16-B vectors: fmx.h)
+    if (!ws_ok(d_ws, ws_bytes)) return FMX_E_ARG;
     hipStream_t s = stream ? (hipStream_t)stream : ix->stream;
     DeviceGuard dg(ix->device);
-    if (n == 0) {
-        hipError_t e = hipMemsetAsync(d_loc_offsets, 0, 8, s);
-        if (e == hipSuccess) e = hipMemsetAsync(d_needed, 0, 8, s);
-        return dev_err(e);
-    }
+    if (n == 0) return dev_err(zero_locs(d_loc_offsets, d_needed, s));
     if (ws_bytes < ws_bytes_for(ix, n)) return FMX_E_ARG;
     uint8_t *ws = (uint8_t *)d_ws;
     const uint64_t G = locate_tiles_cap(n);
@@ -1215,40 +1221,49 @@ fmx_status fmx_locate_batch_async(fmx_index *ix, const uint8_t *d_bytes, const u
     });
 }
 
+// per in 1..max_per and a slot count (n * per) whose 256-slot tiles a launch
+// takes (launch_locate's limit on patterns, applied to slots)
+static bool slots_shape_ok(uint64_t n, uint32_t per, uint32_t max_per) {
+    return per >= 1 && per <= max_per && n <= (0x7FFFFFFFull * 256) / per;
+}
+
+// What the slot queries' device entries share, after their own argument
+// checks: the optional location outputs (d_loc_offsets null: none, and no
+// workspace) and the workspace for `slots` slots checked, an empty batch's
+// zero offset and total, and `launch(out, status, s)` under the stream's
+// status word and the timer `name`.
+extern "C++" {  // (a template, inside the ABI's extern "C")
+template <typename F>
+static fmx_status slot_query(fmx_index *ix, const char *name, uint64_t n, uint64_t slots, uint64_t *d_loc_offsets,
+                             void *d_locs, uint64_t cap, uint64_t *d_needed, void *d_ws, uint64_t ws_bytes,
+                             void *stream, F &&launch) {
+    const bool loc = d_loc_offsets != nullptr;
+    if (loc) {
+        if (!d_needed || (cap && !d_locs)) return FMX_E_ARG;
+        if (!ws_ok(d_ws, ws_bytes)) return FMX_E_ARG;
+        if (n && ws_bytes < ws_bytes_for(ix, slots)) return FMX_E_ARG;
+    }
+    hipStream_t s = stream ? (hipStream_t)stream : ix->stream;
+    DeviceGuard dg(ix->device);
+    if (n == 0) return loc ? dev_err(zero_locs(d_loc_offsets, d_needed, s)) : FMX_OK;
+    const LocOut out{d_loc_offsets, d_locs, cap, d_needed, loc ? (uint64_t *)((uint8_t *)d_ws + kWsHeader) : nullptr,
+                     locate_tiles_cap(slots)};
+    return with_status(ix, s, [&](uint32_t *status) {
+        return dev_err(timed(ix, name, s, slots, [&] { return launch(out, status, s); }));
+    });
+}
+}
+
 fmx_status fmx_match_batch_async(fmx_index *ix, const uint8_t *d_bytes, const uint64_t *d_offsets, uint64_t n,
                                  uint32_t flags, uint32_t min_len, uint64_t max_occ, uint32_t *d_lens, void *d_ranges,
                                  uint64_t *d_loc_offsets, void *d_locs, uint64_t cap, uint64_t *d_needed, void *d_ws,
                                  uint64_t ws_bytes, void *stream) {
     if (!ix || (n && (!d_bytes || !d_offsets || !d_lens || !d_ranges))) return FMX_E_ARG;
-    const bool loc = d_loc_offsets != nullptr;  // (else: lengths and intervals only, no workspace)
-    if (loc) {
-        if (!d_needed || (cap && !d_locs)) return FMX_E_ARG;
-        if (!d_ws || ws_bytes < kWsHeader + 16 || ((uintptr_t)d_ws & 15) != 0) return FMX_E_ARG;
-        if (n && ws_bytes < ws_bytes_for(ix, n)) return FMX_E_ARG;
-    }
-    hipStream_t s = stream ? (hipStream_t)stream : ix->stream;
-    DeviceGuard dg(ix->device);
-    if (n == 0) {
-        if (!loc) return FMX_OK;
-        hipError_t e = hipMemsetAsync(d_loc_offsets, 0, 8, s);
-        if (e == hipSuccess) e = hipMemsetAsync(d_needed, 0, 8, s);
-        return dev_err(e);
-    }
-    uint8_t *ws = (uint8_t *)d_ws;
-    const uint64_t G = locate_tiles_cap(n);
-    return with_status(ix, s, [&](uint32_t *status) {
-        return dev_err(timed(ix, "match", s, n, [&] {
-            return launch_match(ix, d_bytes, d_offsets, n, flags, min_len, max_occ, d_lens, d_ranges, d_loc_offsets,
-                                d_locs, cap, d_needed, loc ? (uint64_t *)(ws + kWsHeader) : nullptr, G, status, s);
-        }));
-    });
-}
-
-// max_seeds in range and a slot count (n * max_seeds) whose 256-slot tiles a
-// launch takes (launch_match's limit on patterns, applied to slots)
-static bool seeds_shape_ok(uint64_t n, uint32_t max_seeds) {
-    if (max_seeds < 1 || max_seeds > kMaxSeeds) return false;
-    return n <= (0x7FFFFFFFull * 256) / max_seeds;
+    return slot_query(ix, "match", n, n, d_loc_offsets, d_locs, cap, d_needed, d_ws, ws_bytes, stream,
+                      [&](const LocOut &out, uint32_t *status, hipStream_t s) {
+                          return launch_match(ix, d_bytes, d_offsets, n, flags, min_len, max_occ, d_lens, d_ranges, out,
+                                              status, s);
+                      });
 }
 
 fmx_status fmx_seeds_batch_async(fmx_index *ix, const uint8_t *d_bytes, const uint64_t *d_offsets, uint64_t n,
@@ -1256,39 +1271,18 @@ fmx_status fmx_seeds_batch_async(fmx_index *ix, const uint8_t *d_bytes, const ui
                                  uint32_t *d_nseeds, uint32_t *d_rest, uint32_t *d_spans, void *d_ranges,
                                  uint64_t *d_loc_offsets, void *d_locs, uint64_t cap, uint64_t *d_needed, void *d_ws,
                                  uint64_t ws_bytes, void *stream) {
-    if (!ix || !seeds_shape_ok(n, max_seeds)) return FMX_E_ARG;
+    if (!ix || !slots_shape_ok(n, max_seeds, kMaxSeeds)) return FMX_E_ARG;
     if (n && (!d_bytes || !d_offsets || !d_nseeds || !d_rest || !d_spans || !d_ranges)) return FMX_E_ARG;
-    const bool loc = d_loc_offsets != nullptr;  // (else: spans and intervals only, no workspace)
-    const uint64_t slots = n * max_seeds;
-    if (loc) {
-        if (!d_needed || (cap && !d_locs)) return FMX_E_ARG;
-        if (!d_ws || ws_bytes < kWsHeader + 16 || ((uintptr_t)d_ws & 15) != 0) return FMX_E_ARG;
-        if (n && ws_bytes < ws_bytes_for(ix, slots)) return FMX_E_ARG;
-    }
-    hipStream_t s = stream ? (hipStream_t)stream : ix->stream;
-    DeviceGuard dg(ix->device);
-    if (n == 0) {
-        if (!loc) return FMX_OK;
-        hipError_t e = hipMemsetAsync(d_loc_offsets, 0, 8, s);
-        if (e == hipSuccess) e = hipMemsetAsync(d_needed, 0, 8, s);
-        return dev_err(e);
-    }
-    uint8_t *ws = (uint8_t *)d_ws;
-    const uint64_t G = locate_tiles_cap(slots);
-    return with_status(ix, s, [&](uint32_t *status) {
-        return dev_err(timed(ix, "seeds", s, slots, [&] {
-            return launch_seeds(ix, d_bytes, d_offsets, n, flags, max_seeds, min_len, skip, max_occ, d_nseeds, d_rest,
-                                d_spans, d_ranges, d_loc_offsets, d_locs, cap, d_needed,
-                                loc ? (uint64_t *)(ws + kWsHeader) : nullptr, G, status, s);
-        }));
-    });
+    return slot_query(ix, "seeds", n, n * max_seeds, d_loc_offsets, d_locs, cap, d_needed, d_ws, ws_bytes, stream,
+                      [&](const LocOut &out, uint32_t *status, hipStream_t s) {
+                          return launch_seeds(ix, d_bytes, d_offsets, n, flags, max_seeds, min_len, skip, max_occ,
+                                              d_nseeds, d_rest, d_spans, d_ranges, out, status, s);
+                      });
 }
 
-// max_mm, max_hits and mode in range and a slot count (n * max_hits) whose
-// 256-slot tiles a launch takes (as seeds_shape_ok)
+// max_mm, max_hits and mode in range and a slot count a launch takes
 static bool approx_shape_ok(uint64_t n, uint32_t max_mm, uint32_t max_hits, uint32_t mode) {
-    if (max_mm > kMaxMismatch || max_hits < 1 || max_hits > kMaxHits || (mode & ~FMX_APPROX_BEST)) return false;
-    return n <= (0x7FFFFFFFull * 256) / max_hits;
+    return max_mm <= kMaxMismatch && !(mode & ~FMX_APPROX_BEST) && slots_shape_ok(n, max_hits, kMaxHits);
 }
 
 fmx_status fmx_approx_batch_async(fmx_index *ix, const uint8_t *d_bytes, const uint64_t *d_offsets, uint64_t n,
@@ -1298,30 +1292,11 @@ fmx_status fmx_approx_batch_async(fmx_index *ix, const uint8_t *d_bytes, const u
                                   uint64_t *d_needed, void *d_ws, uint64_t ws_bytes, void *stream) {
     if (!ix || !approx_shape_ok(n, max_mm, max_hits, mode)) return FMX_E_ARG;
     if (n && (!d_bytes || !d_offsets || !d_nhits || !d_more || !d_mm || !d_subs || !d_ranges)) return FMX_E_ARG;
-    const bool loc = d_loc_offsets != nullptr;  // (else: intervals only, no workspace)
-    const uint64_t slots = n * max_hits;
-    if (loc) {
-        if (!d_needed || (cap && !d_locs)) return FMX_E_ARG;
-        if (!d_ws || ws_bytes < kWsHeader + 16 || ((uintptr_t)d_ws & 15) != 0) return FMX_E_ARG;
-        if (n && ws_bytes < ws_bytes_for(ix, slots)) return FMX_E_ARG;
-    }
-    hipStream_t s = stream ? (hipStream_t)stream : ix->stream;
-    DeviceGuard dg(ix->device);
-    if (n == 0) {
-        if (!loc) return FMX_OK;
-        hipError_t e = hipMemsetAsync(d_loc_offsets, 0, 8, s);
-        if (e == hipSuccess) e = hipMemsetAsync(d_needed, 0, 8, s);
-        return dev_err(e);
-    }
-    uint8_t *ws = (uint8_t *)d_ws;
-    const uint64_t G = locate_tiles_cap(slots);
-    return with_status(ix, s, [&](uint32_t *status) {
-        return dev_err(timed(ix, "approx", s, slots, [&] {
-            return launch_approx(ix, d_bytes, d_offsets, n, flags, max_mm, max_hits, mode, max_occ, d_nhits, d_more,
-                                 d_mm, d_subs, d_ranges, d_loc_offsets, d_locs, cap, d_needed,
-                                 loc ? (uint64_t *)(ws + kWsHeader) : nullptr, G, status, s);
-        }));
-    });
+    return slot_query(ix, "approx", n, n * max_hits, d_loc_offsets, d_locs, cap, d_needed, d_ws, ws_bytes, stream,
+                      [&](const LocOut &out, uint32_t *status, hipStream_t s) {
+                          return launch_approx(ix, d_bytes, d_offsets, n, flags, max_mm, max_hits, mode, max_occ,
+                                               d_nhits, d_more, d_mm, d_subs, d_ranges, out, status, s);
+                      });
 }
 
 fmx_status fmx_locate_jobs_async(fmx_index *ix, const fmx_locate_job *jobs, uint64_t n_jobs) {
@@ -1366,9 +1341,7 @@ fmx_status fmx_locate_group_async(fmx_index *ix, const fmx_locate_job *jobs, uin
         for (; i < n_jobs; ++i) {
             const fmx_locate_job &j = jobs[i];
             if (j.n_patterns == 0) {
-                hipError_t e = hipMemsetAsync(j.d_loc_offsets, 0, 8, s);
-                if (e == hipSuccess) e = hipMemsetAsync(j.d_needed, 0, 8, s);
-                if (e != hipSuccess) return FMX_E_DEVICE;
+                if (zero_locs(j.d_loc_offsets, j.d_needed, s) != hipSuccess) return FMX_E_DEVICE;
                 continue;
             }
             if (grps[ng].n == kMaxGroup) {  // the next group
@@ -1381,7 +1354,7 @@ fmx_status fmx_locate_group_async(fmx_index *ix, const fmx_locate_job *jobs, uin
             grp.tile_begin[grp.n] = tiles;
             grp.b[grp.n++] = LocateBatch{j.d_bytes, j.d_offsets, j.n_patterns, j.d_counts, j.d_loc_offsets,
                                          j.d_locs, j.cap, j.d_needed, (uint64_t *)((uint8_t *)j.d_workspace + kWsHeader),
-                                         (j.flags & FMX_PATTERN_REVERSED) ? 1u : 0u, j.flags >> 16};
+                                         flags_rev(j.flags), flags_stride(j.flags)};
             tiles += (uint32_t)G;
             units += j.n_patterns;
             // the launch stages with the largest hint of its batches
@@ -1491,61 +1464,125 @@ static fmx_status ensure_ws(fmx_index *ix, uint64_t n) {
     return FMX_OK;
 }
 
+// Offsets that start at zero and never decrease, and bytes where there are
+// any: what the slot queries ask (an empty pattern is no error there: its
+// match has length 0; check_patterns rejects it for count and locate).
+static bool offsets_ok(const uint8_t *bytes, const uint64_t *offsets, uint64_t n) {
+    if (offsets[0] != 0) return false;
+    for (uint64_t i = 0; i < n; ++i)
+        if (offsets[i + 1] < offsets[i]) return false;
+    return !offsets[n] || bytes;
+}
+
+// A host call's carve-up of the index's scratch: a running offset, every part
+// 256-B aligned.  The patterns come first (bytes at 0, then the offsets), then
+// the call's own outputs, each remembered with its host destination, then —
+// with locations — the slots' offsets, the total and the locations themselves,
+// the last part, whose size is the device capacity of the pass (host_query).
+struct Carve {
+    struct Out {
+        uint64_t off, bytes;
+        void *host;
+    };
+    uint64_t end = 0, o_off = 0, o_loff = 0, o_need = 0, o_locs = 0;
+    Out outs[8];
+    uint32_t n_outs = 0;
+    uint32_t flags;  // the caller's direction with the batch's own hints (stage_hint)
+    Carve(const uint64_t *offsets, uint64_t n, uint32_t flags_) : flags((flags_ & 0xffu) | stage_hint(offsets, n)) {
+        add(std::max<uint64_t>(offsets[n], 1));
+        o_off = add((n + 1) * 8);
+    }
+    uint64_t add(uint64_t bytes, void *host = nullptr) {
+        const uint64_t o = end;
+        end += align_up(bytes, 256);
+        if (host) outs[n_outs++] = Out{o, bytes, host};
+        return o;
+    }
+    void add_locs(uint64_t slots) {
+        o_loff = add((slots + 1) * 8);
+        o_need = add(8);
+        o_locs = end;
+    }
+};
+
+// One host-buffer query over the index's scratch and workspace: the patterns
+// up, `launch(d, dcap, s)` — the device entry over the parts of scratch base d,
+// with room for dcap locations —, the total and the launch's status, then every
+// output part, the slots' offsets and the locations down (FMX_E_CAPACITY, with
+// everything but the locations, when the caller's cap is short).  out_loc_offsets
+// null: no locations, no workspace.  grow: the device capacity is a guess (one
+// occurrence per slot, or what scratch already holds) and a second pass runs
+// with room for every location when it was short; else the device output has
+// the caller's cap and there is one pass.  (The callers check the offsets and
+// carve before the lock is taken here: both read only the caller's arrays and
+// the index's layout, which is fixed at load — nothing that ix->mu guards.)
+extern "C++" {  // (a template, inside the ABI's extern "C")
+template <typename F>
+static fmx_status host_query(fmx_index *ix, Carve &c, const uint8_t *bytes, const uint64_t *offsets, uint64_t n,
+                             uint64_t slots, bool grow, uint64_t *out_loc_offsets, void *out_locs, uint64_t cap,
+                             uint64_t *needed, F &&launch) {
+    std::lock_guard<std::mutex> g(ix->mu);
+    DeviceGuard dg(ix->device);
+    const bool loc = out_loc_offsets != nullptr;
+    const uint64_t pb = ix->bv.L.pos_bytes;
+    fmx_status st = loc ? ensure_ws(ix, slots) : FMX_OK;
+    if (st) return st;
+    if (loc) c.add_locs(slots);
+    if (loc && !grow && cap > (~0ull - c.o_locs) / pb) return FMX_E_ARG;
+    hipStream_t s = ix->stream;
+    uint64_t dcap = !loc ? 0 : !grow ? cap : std::min<uint64_t>(cap, std::max<uint64_t>(
+        slots, ix->scratch_bytes > c.o_locs ? (ix->scratch_bytes - c.o_locs) / pb : 0));
+    for (int pass = 0; pass < 2; ++pass) {
+        st = ensure_scratch(ix, loc ? c.o_locs + std::max<uint64_t>(dcap, 1) * pb : c.end);
+        if (st) return st;
+        uint8_t *d = ix->d_scratch;
+        hipError_t e = ix->stage.h2d(d, bytes, offsets[n], s);
+        if (e == hipSuccess) e = ix->stage.h2d(d + c.o_off, offsets, (n + 1) * 8, s);
+        if (e != hipSuccess) return FMX_E_DEVICE;
+        st = launch(d, dcap, s);
+        if (st) return st;
+        uint64_t total = 0;
+        if (loc && ix->stage.d2h(&total, d + c.o_need, 8, s) != hipSuccess) return FMX_E_DEVICE;
+        st = read_status(ix, s);
+        if (st) return st;
+        if (needed) *needed = total;
+        if (total > dcap && total <= cap) {
+            dcap = total;  // second pass with room for every location
+            continue;
+        }
+        for (uint32_t j = 0; e == hipSuccess && j < c.n_outs; ++j)
+            e = ix->stage.d2h(c.outs[j].host, d + c.outs[j].off, c.outs[j].bytes, s);
+        if (e == hipSuccess && loc) e = ix->stage.d2h(out_loc_offsets, d + c.o_loff, (slots + 1) * 8, s);
+        if (e != hipSuccess) return FMX_E_DEVICE;
+        if (total > cap) return FMX_E_CAPACITY;
+        if (total) e = ix->stage.d2h(out_locs, d + c.o_locs, total * pb, s);
+        return dev_err(e);
+    }
+    return FMX_E_DEVICE;
+}
+}
+
 fmx_status fmx_locate_batch(fmx_index *ix, const uint8_t *bytes, const uint64_t *offsets, uint64_t n,
                             uint32_t flags, uint64_t *out_loc_offsets, void *out_locs, uint64_t cap,
                             uint64_t *needed) {
     if (!ix || !out_loc_offsets || (n && !offsets) || (cap && !out_locs)) return FMX_E_ARG;
     if (needed) *needed = 0;
     if (n == 0) { out_loc_offsets[0] = 0; return FMX_OK; }
-    std::lock_guard<std::mutex> g(ix->mu);
-    fmx_status st = check_patterns(offsets, n);
+    const fmx_status st = check_patterns(offsets, n);
     if (st) return st;
-    DeviceGuard dg(ix->device);
-    const uint64_t nb = offsets[n], pb = ix->bv.L.pos_bytes;
-    flags = (flags & 0xffu) | stage_hint(offsets, n);
-    st = ensure_ws(ix, n);
-    if (st) return st;
-    const uint64_t o_off = align_up(nb, 256);
-    const uint64_t o_loff = o_off + align_up((n + 1) * 8, 256);
-    const uint64_t o_need = o_loff + align_up((n + 1) * 8, 256);
-    const uint64_t o_locs = o_need + 256;
-    hipStream_t s = ix->stream;
-    // Guess the output size (one occurrence per pattern, or what scratch
-    // already holds); if the patterns have more occurrences, grow and rerun.
-    uint64_t dcap = std::min<uint64_t>(cap, std::max<uint64_t>(n, ix->scratch_bytes > o_locs
-                                                                       ? (ix->scratch_bytes - o_locs) / pb : 0));
-    for (int pass = 0; pass < 2; ++pass) {
-        st = ensure_scratch(ix, o_locs + std::max<uint64_t>(dcap, 1) * pb);
-        if (st) return st;
-        uint8_t *d = ix->d_scratch;
-        hipError_t e = ix->stage.h2d(d, bytes, nb, s);
-        if (e == hipSuccess) e = ix->stage.h2d(d + o_off, offsets, (n + 1) * 8, s);
-        if (e != hipSuccess) return FMX_E_DEVICE;
-        st = fmx_locate_batch_async(ix, d, (uint64_t *)(d + o_off), n, flags, nullptr, (uint64_t *)(d + o_loff),
-                                    d + o_locs, dcap, (uint64_t *)(d + o_need), ix->d_ws, ix->ws_bytes, s);
-        if (st) return st;
-        uint64_t total = 0;
-        if (ix->stage.d2h(&total, d + o_need, 8, s) != hipSuccess) return FMX_E_DEVICE;
-        st = read_status(ix, s);
-        if (st) return st;
-        if (needed) *needed = total;
-        if (total > cap) {
-            if (ix->stage.d2h(out_loc_offsets, d + o_loff, (n + 1) * 8, s) != hipSuccess) return FMX_E_DEVICE;
-            return FMX_E_CAPACITY;
-        }
-        if (total <= dcap) {
-            e = ix->stage.d2h(out_loc_offsets, d + o_loff, (n + 1) * 8, s);
-            if (e == hipSuccess && total) e = ix->stage.d2h(out_locs, d + o_locs, total * pb, s);
-            return dev_err(e);
-        }
-        dcap = total;  // second pass with room for every location
-    }
-    return FMX_E_DEVICE;
+    Carve c(offsets, n, flags);
+    return host_query(ix, c, bytes, offsets, n, n, true, out_loc_offsets, out_locs, cap, needed,
+                      [&](uint8_t *d, uint64_t dcap, hipStream_t s) {
+                          return fmx_locate_batch_async(ix, d, (uint64_t *)(d + c.o_off), n, c.flags, nullptr,
+                                                        (uint64_t *)(d + c.o_loff), d + c.o_locs, dcap,
+                                                        (uint64_t *)(d + c.o_need), ix->d_ws, ix->ws_bytes, s);
+                      });
 }
 
-// Longest-suffix match of a host batch: as fmx_locate_batch (same scratch,
-// workspace, capacity contract and output-size retry), plus the lengths and
-// intervals.  An empty pattern is no error here (its length is 0).
+// The slot queries of a host batch.  An empty pattern is no error here.  With
+// locations, k_scan / k_emit's outputs follow the query's own in scratch.
+
+// Longest-suffix match: the output size guessed and retried as fmx_locate_batch does.
 fmx_status fmx_match_batch(fmx_index *ix, const uint8_t *bytes, const uint64_t *offsets, uint64_t n, uint32_t flags,
                            uint32_t min_len, uint64_t max_occ, uint32_t *out_lens, void *out_ranges,
                            uint64_t *out_loc_offsets, void *out_locs, uint64_t cap, uint64_t *needed) {
@@ -1556,67 +1593,26 @@ fmx_status fmx_match_batch(fmx_index *ix, const uint8_t *bytes, const uint64_t *
         if (loc) out_loc_offsets[0] = 0;
         return FMX_OK;
     }
-    if (offsets[0] != 0) return FMX_E_ARG;
-    for (uint64_t i = 0; i < n; ++i)
-        if (offsets[i + 1] < offsets[i]) return FMX_E_ARG;
-    if (offsets[n] && !bytes) return FMX_E_ARG;
-    std::lock_guard<std::mutex> g(ix->mu);
-    DeviceGuard dg(ix->device);
-    const uint64_t nb = offsets[n], pb = ix->bv.L.pos_bytes;
-    flags = (flags & 0xffu) | stage_hint(offsets, n);
-    fmx_status st = loc ? ensure_ws(ix, n) : FMX_OK;
-    if (st) return st;
-    const uint64_t o_off = align_up(std::max<uint64_t>(nb, 1), 256);
-    const uint64_t o_len = o_off + align_up((n + 1) * 8, 256);
-    const uint64_t o_rng = o_len + align_up(n * 4, 256);
-    const uint64_t o_loff = o_rng + align_up(2 * n * pb, 256);
-    const uint64_t o_need = o_loff + align_up((n + 1) * 8, 256);
-    const uint64_t o_locs = o_need + 256;
-    hipStream_t s = ix->stream;
-    // the output size guessed as fmx_locate_batch does; a second pass if it was short
-    uint64_t dcap = loc ? std::min<uint64_t>(cap, std::max<uint64_t>(n, ix->scratch_bytes > o_locs
-                                                                             ? (ix->scratch_bytes - o_locs) / pb : 0))
-                        : 0;
-    for (int pass = 0; pass < 2; ++pass) {
-        st = ensure_scratch(ix, loc ? o_locs + std::max<uint64_t>(dcap, 1) * pb : o_loff);
-        if (st) return st;
-        uint8_t *d = ix->d_scratch;
-        hipError_t e = ix->stage.h2d(d, bytes, nb, s);
-        if (e == hipSuccess) e = ix->stage.h2d(d + o_off, offsets, (n + 1) * 8, s);
-        if (e != hipSuccess) return FMX_E_DEVICE;
-        st = fmx_match_batch_async(ix, d, (uint64_t *)(d + o_off), n, flags, min_len, max_occ, (uint32_t *)(d + o_len),
-                                   d + o_rng, loc ? (uint64_t *)(d + o_loff) : nullptr, d + o_locs, dcap,
-                                   (uint64_t *)(d + o_need), ix->d_ws, ix->ws_bytes, s);
-        if (st) return st;
-        uint64_t total = 0;
-        if (loc && ix->stage.d2h(&total, d + o_need, 8, s) != hipSuccess) return FMX_E_DEVICE;
-        st = read_status(ix, s);
-        if (st) return st;
-        if (needed) *needed = total;
-        if (total > dcap && total <= cap) {
-            dcap = total;  // second pass with room for every location
-            continue;
-        }
-        e = ix->stage.d2h(out_lens, d + o_len, n * 4, s);
-        if (e == hipSuccess) e = ix->stage.d2h(out_ranges, d + o_rng, 2 * n * pb, s);
-        if (e == hipSuccess && loc) e = ix->stage.d2h(out_loc_offsets, d + o_loff, (n + 1) * 8, s);
-        if (e != hipSuccess) return FMX_E_DEVICE;
-        if (total > cap) return FMX_E_CAPACITY;
-        if (total) e = ix->stage.d2h(out_locs, d + o_locs, total * pb, s);
-        return dev_err(e);
-    }
-    return FMX_E_DEVICE;
+    if (!offsets_ok(bytes, offsets, n)) return FMX_E_ARG;
+    Carve c(offsets, n, flags);
+    const uint64_t o_len = c.add(n * 4, out_lens), o_rng = c.add(2 * n * ix->bv.L.pos_bytes, out_ranges);
+    return host_query(ix, c, bytes, offsets, n, n, true, out_loc_offsets, out_locs, cap, needed,
+                      [&](uint8_t *d, uint64_t dcap, hipStream_t s) {
+                          return fmx_match_batch_async(ix, d, (uint64_t *)(d + c.o_off), n, c.flags, min_len, max_occ,
+                                                       (uint32_t *)(d + o_len), d + o_rng,
+                                                       loc ? (uint64_t *)(d + c.o_loff) : nullptr, d + c.o_locs, dcap,
+                                                       (uint64_t *)(d + c.o_need), ix->d_ws, ix->ws_bytes, s);
+                      });
 }
 
-// Greedy seed chains of a host batch: upload, one fmx_seeds_batch_async over
-// the index's scratch and workspace, download.  No retry: the device output
-// has the caller's cap, and the capacity contract is the caller's.
+// Greedy seed chains.  No retry: the device output has the caller's cap, and
+// the capacity contract is the caller's.
 fmx_status fmx_seeds_batch(fmx_index *ix, const uint8_t *bytes, const uint64_t *offsets, uint64_t n, uint32_t flags,
                            uint32_t max_seeds, uint32_t min_len, uint32_t skip, uint64_t max_occ, uint32_t *out_nseeds,
                            uint32_t *out_rest, uint32_t *out_spans, void *out_ranges, uint64_t *out_loc_offsets,
                            void *out_locs, uint64_t cap, uint64_t *needed) {
     const bool loc = out_loc_offsets != nullptr;
-    if (!ix || !seeds_shape_ok(n, max_seeds)) return FMX_E_ARG;
+    if (!ix || !slots_shape_ok(n, max_seeds, kMaxSeeds)) return FMX_E_ARG;
     if ((n && (!offsets || !out_nseeds || !out_rest || !out_spans || !out_ranges)) || (loc && cap && !out_locs))
         return FMX_E_ARG;
     if (needed) *needed = 0;
@@ -1624,55 +1620,22 @@ fmx_status fmx_seeds_batch(fmx_index *ix, const uint8_t *bytes, const uint64_t *
         if (loc) out_loc_offsets[0] = 0;
         return FMX_OK;
     }
-    if (offsets[0] != 0) return FMX_E_ARG;
-    for (uint64_t i = 0; i < n; ++i)
-        if (offsets[i + 1] < offsets[i]) return FMX_E_ARG;
-    if (offsets[n] && !bytes) return FMX_E_ARG;
-    std::lock_guard<std::mutex> g(ix->mu);
-    DeviceGuard dg(ix->device);
-    const uint64_t nb = offsets[n], pb = ix->bv.L.pos_bytes, slots = n * max_seeds;
-    flags = (flags & 0xffu) | stage_hint(offsets, n);
-    fmx_status st = loc ? ensure_ws(ix, slots) : FMX_OK;
-    if (st) return st;
-    const uint64_t o_off = align_up(std::max<uint64_t>(nb, 1), 256);
-    const uint64_t o_ns = o_off + align_up((n + 1) * 8, 256);
-    const uint64_t o_rest = o_ns + align_up(n * 4, 256);
-    const uint64_t o_span = o_rest + align_up(n * 4, 256);
-    const uint64_t o_rng = o_span + align_up(2 * slots * 4, 256);
-    const uint64_t o_loff = o_rng + align_up(2 * slots * pb, 256);
-    const uint64_t o_need = o_loff + align_up((slots + 1) * 8, 256);
-    const uint64_t o_locs = o_need + 256;
-    if (loc && cap > (~0ull - o_locs) / pb) return FMX_E_ARG;
-    hipStream_t s = ix->stream;
-    st = ensure_scratch(ix, loc ? o_locs + std::max<uint64_t>(cap, 1) * pb : o_loff);
-    if (st) return st;
-    uint8_t *d = ix->d_scratch;
-    hipError_t e = ix->stage.h2d(d, bytes, nb, s);
-    if (e == hipSuccess) e = ix->stage.h2d(d + o_off, offsets, (n + 1) * 8, s);
-    if (e != hipSuccess) return FMX_E_DEVICE;
-    st = fmx_seeds_batch_async(ix, d, (uint64_t *)(d + o_off), n, flags, max_seeds, min_len, skip, max_occ,
-                               (uint32_t *)(d + o_ns), (uint32_t *)(d + o_rest), (uint32_t *)(d + o_span), d + o_rng,
-                               loc ? (uint64_t *)(d + o_loff) : nullptr, d + o_locs, cap, (uint64_t *)(d + o_need),
-                               ix->d_ws, ix->ws_bytes, s);
-    if (st) return st;
-    uint64_t total = 0;
-    if (loc && ix->stage.d2h(&total, d + o_need, 8, s) != hipSuccess) return FMX_E_DEVICE;
-    st = read_status(ix, s);
-    if (st) return st;
-    if (needed) *needed = total;
-    e = ix->stage.d2h(out_nseeds, d + o_ns, n * 4, s);
-    if (e == hipSuccess) e = ix->stage.d2h(out_rest, d + o_rest, n * 4, s);
-    if (e == hipSuccess) e = ix->stage.d2h(out_spans, d + o_span, 2 * slots * 4, s);
-    if (e == hipSuccess) e = ix->stage.d2h(out_ranges, d + o_rng, 2 * slots * pb, s);
-    if (e == hipSuccess && loc) e = ix->stage.d2h(out_loc_offsets, d + o_loff, (slots + 1) * 8, s);
-    if (e != hipSuccess) return FMX_E_DEVICE;
-    if (total > cap) return FMX_E_CAPACITY;
-    if (total) e = ix->stage.d2h(out_locs, d + o_locs, total * pb, s);
-    return dev_err(e);
+    if (!offsets_ok(bytes, offsets, n)) return FMX_E_ARG;
+    const uint64_t pb = ix->bv.L.pos_bytes, slots = n * max_seeds;
+    Carve c(offsets, n, flags);
+    const uint64_t o_ns = c.add(n * 4, out_nseeds), o_rest = c.add(n * 4, out_rest);
+    const uint64_t o_span = c.add(2 * slots * 4, out_spans), o_rng = c.add(2 * slots * pb, out_ranges);
+    return host_query(ix, c, bytes, offsets, n, slots, false, out_loc_offsets, out_locs, cap, needed,
+                      [&](uint8_t *d, uint64_t dcap, hipStream_t s) {
+                          return fmx_seeds_batch_async(ix, d, (uint64_t *)(d + c.o_off), n, c.flags, max_seeds, min_len,
+                                                       skip, max_occ, (uint32_t *)(d + o_ns), (uint32_t *)(d + o_rest),
+                                                       (uint32_t *)(d + o_span), d + o_rng,
+                                                       loc ? (uint64_t *)(d + c.o_loff) : nullptr, d + c.o_locs, dcap,
+                                                       (uint64_t *)(d + c.o_need), ix->d_ws, ix->ws_bytes, s);
+                      });
 }
 
-// k-mismatch search of a host batch: upload, one fmx_approx_batch_async over
-// the index's scratch and workspace, download.  No retry, as fmx_seeds_batch.
+// k-mismatch search.  No retry, as fmx_seeds_batch.
 fmx_status fmx_approx_batch(fmx_index *ix, const uint8_t *bytes, const uint64_t *offsets, uint64_t n, uint32_t flags,
                             uint32_t max_mm, uint32_t max_hits, uint32_t mode, uint64_t max_occ, uint32_t *out_nhits,
                             uint32_t *out_more, uint32_t *out_mm, uint32_t *out_subs, void *out_ranges,
@@ -1687,53 +1650,19 @@ fmx_status fmx_approx_batch(fmx_index *ix, const uint8_t *bytes, const uint64_t 
         if (loc) out_loc_offsets[0] = 0;
         return FMX_OK;
     }
-    if (offsets[0] != 0) return FMX_E_ARG;
-    for (uint64_t i = 0; i < n; ++i)
-        if (offsets[i + 1] < offsets[i]) return FMX_E_ARG;
-    if (offsets[n] && !bytes) return FMX_E_ARG;
-    std::lock_guard<std::mutex> g(ix->mu);
-    DeviceGuard dg(ix->device);
-    const uint64_t nb = offsets[n], pb = ix->bv.L.pos_bytes, slots = n * max_hits;
-    flags = (flags & 0xffu) | stage_hint(offsets, n);
-    fmx_status st = loc ? ensure_ws(ix, slots) : FMX_OK;
-    if (st) return st;
-    const uint64_t o_off = align_up(std::max<uint64_t>(nb, 1), 256);
-    const uint64_t o_nh = o_off + align_up((n + 1) * 8, 256);
-    const uint64_t o_more = o_nh + align_up(n * 4, 256);
-    const uint64_t o_mm = o_more + align_up(n * 4, 256);
-    const uint64_t o_subs = o_mm + align_up(slots * 4, 256);
-    const uint64_t o_rng = o_subs + align_up(6 * slots * 4, 256);
-    const uint64_t o_loff = o_rng + align_up(2 * slots * pb, 256);
-    const uint64_t o_need = o_loff + align_up((slots + 1) * 8, 256);
-    const uint64_t o_locs = o_need + 256;
-    if (loc && cap > (~0ull - o_locs) / pb) return FMX_E_ARG;
-    hipStream_t s = ix->stream;
-    st = ensure_scratch(ix, loc ? o_locs + std::max<uint64_t>(cap, 1) * pb : o_loff);
-    if (st) return st;
-    uint8_t *d = ix->d_scratch;
-    hipError_t e = ix->stage.h2d(d, bytes, nb, s);
-    if (e == hipSuccess) e = ix->stage.h2d(d + o_off, offsets, (n + 1) * 8, s);
-    if (e != hipSuccess) return FMX_E_DEVICE;
-    st = fmx_approx_batch_async(ix, d, (uint64_t *)(d + o_off), n, flags, max_mm, max_hits, mode, max_occ,
-                                (uint32_t *)(d + o_nh), (uint32_t *)(d + o_more), (uint32_t *)(d + o_mm),
-                                (uint32_t *)(d + o_subs), d + o_rng, loc ? (uint64_t *)(d + o_loff) : nullptr,
-                                d + o_locs, cap, (uint64_t *)(d + o_need), ix->d_ws, ix->ws_bytes, s);
-    if (st) return st;
-    uint64_t total = 0;
-    if (loc && ix->stage.d2h(&total, d + o_need, 8, s) != hipSuccess) return FMX_E_DEVICE;
-    st = read_status(ix, s);
-    if (st) return st;
-    if (needed) *needed = total;
-    e = ix->stage.d2h(out_nhits, d + o_nh, n * 4, s);
-    if (e == hipSuccess) e = ix->stage.d2h(out_more, d + o_more, n * 4, s);
-    if (e == hipSuccess) e = ix->stage.d2h(out_mm, d + o_mm, slots * 4, s);
-    if (e == hipSuccess) e = ix->stage.d2h(out_subs, d + o_subs, 6 * slots * 4, s);
-    if (e == hipSuccess) e = ix->stage.d2h(out_ranges, d + o_rng, 2 * slots * pb, s);
-    if (e == hipSuccess && loc) e = ix->stage.d2h(out_loc_offsets, d + o_loff, (slots + 1) * 8, s);
-    if (e != hipSuccess) return FMX_E_DEVICE;
-    if (total > cap) return FMX_E_CAPACITY;
-    if (total) e = ix->stage.d2h(out_locs, d + o_locs, total * pb, s);
-    return dev_err(e);
+    if (!offsets_ok(bytes, offsets, n)) return FMX_E_ARG;
+    const uint64_t pb = ix->bv.L.pos_bytes, slots = n * max_hits;
+    Carve c(offsets, n, flags);
+    const uint64_t o_nh = c.add(n * 4, out_nhits), o_more = c.add(n * 4, out_more), o_mm = c.add(slots * 4, out_mm);
+    const uint64_t o_subs = c.add(6 * slots * 4, out_subs), o_rng = c.add(2 * slots * pb, out_ranges);
+    return host_query(ix, c, bytes, offsets, n, slots, false, out_loc_offsets, out_locs, cap, needed,
+                      [&](uint8_t *d, uint64_t dcap, hipStream_t s) {
+                          return fmx_approx_batch_async(ix, d, (uint64_t *)(d + c.o_off), n, c.flags, max_mm, max_hits,
+                                                        mode, max_occ, (uint32_t *)(d + o_nh), (uint32_t *)(d + o_more),
+                                                        (uint32_t *)(d + o_mm), (uint32_t *)(d + o_subs), d + o_rng,
+                                                        loc ? (uint64_t *)(d + c.o_loff) : nullptr, d + c.o_locs, dcap,
+                                                        (uint64_t *)(d + c.o_need), ix->d_ws, ix->ws_bytes, s);
+                      });
 }
 
 // ---------------------------------------------------------------- timing

@@ -350,10 +350,28 @@ inline void group_reset(LocateGroup &g) {
     g.gn = g.vbase = 0;
     g.tickets = nullptr;
 }
-// One longest-suffix match batch (k_match; fmx_match_batch_async): every
-// pattern's matched length and interval; with recs (the locate workspace's
-// search records, after its 2 G tile words at `tiles`) also the record and
-// the tile counts that k_scan / k_emit turn into offsets and locations.
+// The slot queries (k_match, k_seeds, k_approx; DESIGN.md, "Slot queries").
+// A query of npat patterns has `slots` = npat * per output slots, pattern i
+// owning the `per` slots from i * per (k_match: one, the pattern itself).  With
+// `tiles` — the locate workspace of `slots` "patterns": G = ceil(slots / 256)
+// tile counts, G tile offsets, then a search record per slot — the kernel also
+// leaves every slot's record and the tile counts, and k_scan / k_emit turn them
+// into offsets and locations exactly as for a locate of `slots` patterns.  In
+// launch order only.
+//
+// The optional location outputs of such a launch, and its workspace.
+struct LocOut {
+    uint64_t *loc_offsets;  // null: no locations (the other fields unused)
+    void *locs;
+    uint64_t cap;
+    uint64_t *needed;
+    uint64_t *tiles;  // the workspace past its header (kWsHeader)
+    uint64_t tiles_cap;
+};
+// FMX_PATTERN_REVERSED and FMX_HINT_FIXED_LEN of a call's flags, as the batch structs hold them
+inline uint32_t flags_rev(uint32_t flags) { return (flags & FMX_PATTERN_REVERSED) ? 1u : 0u; }
+inline uint32_t flags_stride(uint32_t flags) { return flags >> 16; }
+// k_match: every pattern's matched length and interval.
 struct MatchBatch {
     const uint8_t *bytes;
     const uint64_t *offs;
@@ -366,17 +384,10 @@ struct MatchBatch {
     uint32_t rev;
     uint32_t stride;  // FMX_HINT_FIXED_LEN (0: read the offsets)
 };
-// k_match, then (d_loc_offsets non-null) k_scan / k_emit over the records it
-// left: d_tiles as for launch_locate.  In launch order only.
 hipError_t launch_match(const fmx_index *ix, const uint8_t *d_bytes, const uint64_t *d_offsets, uint64_t n,
                         uint32_t flags, uint32_t min_len, uint64_t max_occ, uint32_t *d_lens, void *d_ranges,
-                        uint64_t *d_loc_offsets, void *d_locs, uint64_t cap, uint64_t *d_needed, uint64_t *d_tiles,
-                        uint64_t tiles_cap, uint32_t *status, hipStream_t stream);
-// One greedy seed-chain batch (k_seeds; fmx_seeds_batch_async): pattern i owns
-// the max_seeds slots from i * max_seeds.  With tiles (the locate workspace
-// of npat * max_seeds "patterns": G = ceil(npat max_seeds / 256) tile counts, G
-// tile offsets, then a search record per slot) also every slot's record and
-// the tile counts that k_scan / k_emit turn into offsets and locations.
+                        const LocOut &out, uint32_t *status, hipStream_t stream);
+// k_seeds: max_seeds slots per pattern.
 constexpr uint32_t kMaxSeeds = 32;
 struct SeedBatch {
     const uint8_t *bytes;
@@ -394,17 +405,11 @@ struct SeedBatch {
     uint32_t rev;
     uint32_t stride;  // FMX_HINT_FIXED_LEN (0: read the offsets)
 };
-// k_seeds, then (d_loc_offsets non-null) k_scan / k_emit over the slots'
-// records: d_tiles as for launch_locate of n * max_seeds patterns.  In launch
-// order only.
 hipError_t launch_seeds(const fmx_index *ix, const uint8_t *d_bytes, const uint64_t *d_offsets, uint64_t n,
                         uint32_t flags, uint32_t max_seeds, uint32_t min_len, uint32_t skip, uint64_t max_occ,
-                        uint32_t *d_nseeds, uint32_t *d_rest, uint32_t *d_spans, void *d_ranges,
-                        uint64_t *d_loc_offsets, void *d_locs, uint64_t cap, uint64_t *d_needed, uint64_t *d_tiles,
-                        uint64_t tiles_cap, uint32_t *status, hipStream_t stream);
-// One k-mismatch batch (k_approx; fmx_approx_batch_async): pattern i owns the
-// max_hits slots from i * max_hits, tiles as for SeedBatch (the locate
-// workspace of npat * max_hits "patterns").
+                        uint32_t *d_nseeds, uint32_t *d_rest, uint32_t *d_spans, void *d_ranges, const LocOut &out,
+                        uint32_t *status, hipStream_t stream);
+// k_approx: max_hits slots per pattern.
 constexpr uint32_t kMaxHits = 32;
 constexpr uint32_t kMaxMismatch = 3;
 struct ApproxBatch {
@@ -424,14 +429,10 @@ struct ApproxBatch {
     uint32_t rev;
     uint32_t stride;  // FMX_HINT_FIXED_LEN (0: read the offsets)
 };
-// k_approx, then (d_loc_offsets non-null) k_scan / k_emit over the slots'
-// records: d_tiles as for launch_locate of n * max_hits patterns.  In launch
-// order only.
 hipError_t launch_approx(const fmx_index *ix, const uint8_t *d_bytes, const uint64_t *d_offsets, uint64_t n,
                          uint32_t flags, uint32_t max_mm, uint32_t max_hits, uint32_t mode, uint64_t max_occ,
                          uint32_t *d_nhits, uint32_t *d_more, uint32_t *d_mm, uint32_t *d_subs, void *d_ranges,
-                         uint64_t *d_loc_offsets, void *d_locs, uint64_t cap, uint64_t *d_needed, uint64_t *d_tiles,
-                         uint64_t tiles_cap, uint32_t *status, hipStream_t stream);
+                         const LocOut &out, uint32_t *status, hipStream_t stream);
 // `mid` (optional): an event recorded between k_search and k_emit (timing).
 // Fills grp's per-launch fields (first, emit_begin, the grouped fields) in place.
 hipError_t launch_locate_group(const fmx_index *ix, LocateGroup &grp, uint32_t stage_flags,

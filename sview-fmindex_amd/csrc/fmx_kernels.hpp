@@ -1,5 +1,7 @@
 // fmx_kernels.hpp — the query kernels that depend on the occ layout (P, N,
-// V, record size): k_count, k_search, k_match, k_seeds, k_approx, k_emit, the deep-table level step, the
+// V, record size): k_count, k_search, k_emit, the slot queries (k_match,
+// k_seeds, k_approx: slots, records, tile counts and the reuse of k_scan /
+// k_emit are described once, above them), the deep-table level step, the
 // full-SA walk and the record re-layout.  Instantiated per (P, N) in its own
 // translation unit (fmx_layout.hip, one object per layout, built in
 // parallel); launched through the LayoutOps table (fmx_internal.hpp).
@@ -375,21 +377,105 @@ __global__ __launch_bounds__(256, VAR == kVarDerivedLong ? 4 : 8) void k_search(
     search_tile<P, N, VB, REC, VAR>(a, grp, s, s_pat, s_scan, stage_bytes, blockIdx.x);
 }
 
-// ------------------------------------------------ k_match (longest suffix)
-// One lane per pattern, as k_search: the length of the longest suffix of the
-// pattern that occurs in the text and its interval (match_suffix), always
-// written.  With B.tiles (locations asked for) the lane also leaves the search
-// record k_emit reads — {lo, count, 0}, the count 0 unless the pattern reports
-// (length >= max(min_len, 1) and count <= max_occ); one row located here,
-// while the lane's chain is live, as search_lane does — and the workgroup its
-// tile's count, so that k_scan / k_emit write the offsets, the total and the
-// locations exactly as for a locate.
+// ------------------------------------- slot queries: k_match, k_seeds, k_approx
+// One lane per pattern, as k_search, the workgroup's 256 patterns staged once
+// (lane_pattern; k_match by hand).  Pattern i owns the `per` output SLOTS from i * per — k_match
+// one (the pattern's longest suffix), k_seeds max_seeds (its seeds in order),
+// k_approx max_hits (its variants in the contract's order) — and the kernel
+// always writes every slot's own outputs, the unused slots zero.  Outputs are
+// addressed from the workgroup's first slot (first * per, uniform) by a 32-bit
+// slot number ls = lane * per + j, which keeps the per-lane state small.
+// With B.tiles (locations asked for; workgroup-uniform) every slot also gets
+// the search RECORD k_emit reads (slot_record): {lo, count, 0}, the count 0
+// unless the slot reports (slot_count); one row whose location costs one read
+// is located here, while the lane's chain is live, and stored as k_search
+// stores it ({location, 1, 1}), any other row is left to k_emit's walk; unused
+// slots: zeros (zero_record).  The workspace at B.tiles is the locate's, of npat
+// * per "patterns": G = ceil(npat per / 256) TILE COUNTS, G tile offsets, then
+// the records.  A workgroup's slots are exactly `per` whole 256-slot tiles of
+// k_emit (the last workgroup's: as many as the batch has), so it adds each
+// reporting slot's count to its tile's in LDS and writes the tile counts
+// (store_tile_counts; k_match, one tile per workgroup, sums them with the
+// block scan): k_scan / k_emit then run unchanged over npat * per "patterns"
+// and write the offsets, the total and the locations exactly as for a locate.
+
+// The prologue: the tile's patterns staged (after stage_tables), the barrier,
+// this lane's view of its pattern.  has: the lane has one (pattern first + lane
+// < npat; the view of a lane without is empty — stage_patterns gives it beg =
+// end = 0 and pattern_view is arithmetic only, so m = 0 and nothing is loaded);
+// staged: stage_patterns' result.
+template <typename P>
+__device__ __forceinline__ PatView lane_pattern(const Tables<P> &s, uint8_t *s_pat, const uint8_t *__restrict__ bytes,
+                                                const uint64_t *offs, uint64_t npat, uint64_t first, bool rev,
+                                                uint32_t stage_bytes, uint32_t stride, uint32_t *status, bool &has,
+                                                bool &staged) {
+    uint64_t beg, end, b0, b1;
+    staged = stage_patterns(s, s_pat, bytes, offs, npat, first, rev, stage_bytes, stride, status, beg, end, b0, b1);
+    __syncthreads();
+    has = first + threadIdx.x < npat;
+    return pattern_view(s, s_pat, staged, bytes, beg, end, b0, b1, rev);
+}
+
+// The workgroup's records: after the workspace's 2 G tile words, from the workgroup's first slot.
+template <typename P>
+__device__ __forceinline__ SearchRec<P> *slot_records(uint64_t *tiles, uint64_t G, uint64_t slot0) {
+    return reinterpret_cast<SearchRec<P> *>(tiles + 2 * G) + slot0;
+}
+
+// The rows a slot with interval [lo, hi) reports: all of them, or none when they are more than max_occ.
+template <typename P>
+__device__ __forceinline__ uint64_t slot_count(P lo, P hi, uint64_t max_occ) {
+    return (uint64_t)(hi - lo) <= max_occ ? (uint64_t)(hi - lo) : 0;
+}
+
+// The record of a slot that reports cnt rows from lo; located: its one row's location is `one`.
+template <typename P>
+__device__ __forceinline__ SearchRec<P> make_record(P lo, uint64_t cnt, bool located, P one) {
+    return located ? SearchRec<P>{one, P(1), 1ull} : SearchRec<P>{lo, (P)cnt, 0ull};
+}
+
+// Slot ls of the workgroup: its record, and its count added to its tile's (tile ls >> 8 of the workgroup's).
+// One row not located by the caller is, under a full SA, located here by that one read (walk_row's); a row
+// that needs the walk is left to k_emit as a one-row interval — walk_row inlined into k_seeds, with the view
+// live across it, spilled in 124 of the 280 instantiations against 42 without it (k_match: 12), whatever the
+// occupancy bound.
+template <typename P>
+__device__ __forceinline__ void slot_record(const QueryArgs &a, SearchRec<P> *__restrict__ recs,
+                                            unsigned long long *s_tile, uint32_t ls, P lo, uint64_t cnt,
+                                            bool located = false, P one = 0) {
+    if (located) recs[ls] = make_record<P>(lo, cnt, true, one);
+    else if (cnt == 1 && a.safull != nullptr)
+        recs[ls] = make_record<P>(lo, cnt, true, reinterpret_cast<const P *>(a.safull)[(uint64_t)lo * a.sa_stride]);
+    else recs[ls] = make_record<P>(lo, cnt, false, P(0));
+    if (cnt) atomicAdd(&s_tile[ls >> 8], (unsigned long long)cnt);
+}
+
+template <typename P>
+__device__ __forceinline__ void zero_record(SearchRec<P> *__restrict__ recs, uint32_t ls) {
+    recs[ls] = SearchRec<P>{P(0), P(0), 0ull};
+}
+
+// The epilogue (every thread of the workgroup): its `per` tiles' counts from LDS, of the batch's G.
+__device__ __forceinline__ void store_tile_counts(uint64_t *tiles, const unsigned long long *s_tile, uint32_t per,
+                                                  uint64_t G) {
+    __syncthreads();
+    const uint64_t tile = (uint64_t)blockIdx.x * per + threadIdx.x;
+    if (threadIdx.x < per && tile < G) tiles[tile] = s_tile[threadIdx.x];
+}
+
+// k_match: the length of the longest suffix of the pattern that occurs in the
+// text and its interval (match_suffix), always written.  The slot reports when
+// the length is at least max(min_len, 1) too; its one row is located as
+// search_lane does (locate_one).
 template <typename P, int N, int VB, int REC>
 __global__ __launch_bounds__(256, 8) void k_match(const QueryArgs a, const MatchBatch B, uint32_t stage_bytes) {
     __shared__ Tables<P> s;
     FMX_DYN_LDS(s_pat);  // stage_bytes, then the k-mer table (dynamic)
     __shared__ uint64_t s_scan[4];
     stage_tables(a, s, s_pat + stage_bytes);
+    // (the prologue by hand, as k_count and search_lane have it: with lane_pattern here the compiler changed
+    // an AND mask in the record-518 k_count, k_search, k_locate and k_search_grouped of five layouts,
+    // profiles/r11/README.md)
     const uint8_t *__restrict__ bytes = B.bytes;
     const uint64_t npat = B.npat, first = (uint64_t)blockIdx.x * 256u;
     const bool rev = B.rev != 0;
@@ -411,12 +497,11 @@ __global__ __launch_bounds__(256, 8) void k_match(const QueryArgs a, const Match
         rng[0] = lo;
         rng[1] = hi;
         if (loc) {
-            const uint64_t G = (npat + 255) / 256;
-            SearchRec<P> *__restrict__ recs = reinterpret_cast<SearchRec<P> *>(B.tiles + 2 * G);
+            SearchRec<P> *__restrict__ recs = slot_records<P>(B.tiles, (npat + 255) / 256, 0);
             const uint32_t need = B.min_len > 1u ? B.min_len : 1u;
-            if (len >= need && (uint64_t)(hi - lo) <= B.max_occ) cnt = (uint64_t)(hi - lo);
-            if (cnt == 1) recs[i] = SearchRec<P>{locate_one<P, N, VB, REC>(a, s.C, lo, smp), P(1), 1ull};
-            else recs[i] = SearchRec<P>{lo, (P)cnt, 0ull};
+            if (len >= need) cnt = slot_count<P>(lo, hi, B.max_occ);
+            if (cnt == 1) recs[i] = make_record<P>(lo, cnt, true, locate_one<P, N, VB, REC>(a, s.C, lo, smp));
+            else recs[i] = make_record<P>(lo, cnt, false, P(0));
         }
     }
     if (loc) {
@@ -426,51 +511,37 @@ __global__ __launch_bounds__(256, 8) void k_match(const QueryArgs a, const Match
     }
 }
 
-// ------------------------------------------------ k_seeds (greedy seed chain)
-// One lane per pattern, k_match's shape, the pattern staged once: the lane
-// restarts match_suffix on ever shorter prefixes p[0..e) — a smaller m on the
-// same view (an unstaged reversed pattern, whose at(j) reads raw[m-1-j], also
-// has raw advanced by what m lost) — until the pattern or its max_seeds slots
-// are used up (fmx.h: e -= min(e, max(L + skip, 1)); a match of at least
-// max(min_len, 1) symbols is a seed).  Pattern i owns slots [i max_seeds,
-// (i+1) max_seeds): its seeds' (end, length) and (lo, hi) in order, the unused
-// slots zero.  With B.tiles every slot also gets k_emit's record — {lo, count,
-// 0}, the count 0 unless the seed reports (count <= max_occ; unused slots:
-// zeros); one row with a sampled row seen in that restart's own single-row
-// phase (SampledRow), or under a full SA, located here by that one read, any
-// other left to k_emit's walk — and the workgroup, whose slots are exactly max_seeds whole
-// 256-slot tiles of k_emit (the last workgroup's: as many as the batch has),
-// adds each reporting seed's count to its tile's in LDS and writes the tile
-// counts: k_scan / k_emit then run unchanged over npat max_seeds "patterns".
+// k_seeds: the lane restarts match_suffix on ever shorter prefixes p[0..e) — a
+// smaller m on the same view (an unstaged reversed pattern, whose at(j) reads
+// raw[m-1-j], also has raw advanced by what m lost) — until the pattern or its
+// max_seeds slots are used up (fmx.h: e -= min(e, max(L + skip, 1)); a match of
+// at least max(min_len, 1) symbols is a seed): per slot the seed's (end,
+// length) and (lo, hi).  One row with a sampled row seen in that restart's own
+// single-row phase (SampledRow) is located here by that one read.
 template <typename P, int N, int VB, int REC>
 __global__ __launch_bounds__(256, 8) void k_seeds(const QueryArgs a, const SeedBatch B, uint32_t stage_bytes) {
     __shared__ Tables<P> s;
     FMX_DYN_LDS(s_pat);  // stage_bytes, then the k-mer table (dynamic)
     __shared__ unsigned long long s_tile[kMaxSeeds];
     stage_tables(a, s, s_pat + stage_bytes);
-    if (threadIdx.x < kMaxSeeds) s_tile[threadIdx.x] = 0;  // (visible after stage_patterns' barrier)
-    const uint8_t *__restrict__ bytes = B.bytes;
+    if (threadIdx.x < kMaxSeeds) s_tile[threadIdx.x] = 0;  // (visible after lane_pattern's barrier)
     const uint64_t npat = B.npat, first = (uint64_t)blockIdx.x * 256u;
     const bool rev = B.rev != 0;
-    uint64_t beg, end, b0, b1;
-    const bool staged =
-        stage_patterns(s, s_pat, bytes, B.offs, npat, first, rev, stage_bytes, B.stride, a.status, beg, end, b0, b1);
-    __syncthreads();
-    const uint64_t i = first + threadIdx.x;
+    bool has, staged;
+    PatView pv =
+        lane_pattern(s, s_pat, B.bytes, B.offs, npat, first, rev, stage_bytes, B.stride, a.status, has, staged);
     const uint32_t ms = B.max_seeds;
     const bool loc = B.tiles != nullptr;  // (workgroup-uniform)
     const uint64_t G = (npat * ms + 255) / 256;  // the batch's 256-slot tiles
-    if (i < npat) {
-        PatView pv = pattern_view(s, s_pat, staged, bytes, beg, end, b0, b1, rev);
-        // Per-lane state kept small (<u32,3,64,*> sit at the 64 VGPRs of 8 waves per SIMD): the outputs
-        // are addressed from the workgroup's first slot (uniform) by a 32-bit slot number, and the
-        // prefix's end e is the view's own m.
+    if (has) {
+        // Per-lane state kept small (<u32,3,64,*> sit at the 64 VGPRs of 8 waves per SIMD): the prefix's end e
+        // is the view's own m.
         const uint64_t slot0 = first * ms;
         uint32_t *__restrict__ spans = B.out_spans + 2 * slot0;
         P *__restrict__ rng = reinterpret_cast<P *>(B.out_rng) + 2 * slot0;
         SearchRec<P> *__restrict__ recs = nullptr;
-        if (loc) recs = reinterpret_cast<SearchRec<P> *>(B.tiles + 2 * G) + slot0;
-        uint32_t ls = threadIdx.x * ms;  // seed j's slot in the workgroup: tile ls >> 8 of its max_seeds
+        if (loc) recs = slot_records<P>(B.tiles, G, slot0);
+        uint32_t ls = threadIdx.x * ms;  // seed j's slot in the workgroup
         const uint32_t ls_end = ls + ms;
         const uint32_t need = B.min_len > 1u ? B.min_len : 1u;
         const bool raw_rev = rev && !staged;
@@ -485,22 +556,12 @@ __global__ __launch_bounds__(256, 8) void k_seeds(const QueryArgs a, const SeedB
                 rng[2 * ls] = lo;
                 rng[2 * ls + 1] = hi;
                 if (loc) {
-                    const uint64_t cnt = (uint64_t)(hi - lo) <= B.max_occ ? (uint64_t)(hi - lo) : 0;
-                    // one row: located here when that is one read (this restart's sampled row, or the
-                    // full SA); a row that needs the walk is left to k_emit as a one-row interval —
-                    // walk_row inlined here, with the view live across it, spilled in 124 of the 280
-                    // instantiations against 42 without it (k_match: 12), whatever the occupancy bound
+                    const uint64_t cnt = slot_count<P>(lo, hi, B.max_occ);
                     P one = 0;
-                    bool settled = false;
-                    if (cnt == 1 && smp.valid) {
-                        one = load_once(reinterpret_cast<const P *>(a.sa) + smp.slot) - smp.off;  // (locate_one)
-                        settled = true;
-                    } else if (cnt == 1 && a.safull != nullptr) {
-                        one = reinterpret_cast<const P *>(a.safull)[(uint64_t)lo * a.sa_stride];  // (walk_row)
-                        settled = true;
-                    }
-                    recs[ls] = settled ? SearchRec<P>{one, P(1), 1ull} : SearchRec<P>{lo, (P)cnt, 0ull};
-                    if (cnt) atomicAdd(&s_tile[ls >> 8], (unsigned long long)cnt);
+                    const bool sampled = cnt == 1 && smp.valid;
+                    if (sampled)  // (locate_one)
+                        one = load_once(reinterpret_cast<const P *>(a.sa) + smp.slot) - smp.off;
+                    slot_record<P>(a, recs, s_tile, ls, lo, cnt, sampled, one);
                 }
                 ++ls;
             }
@@ -514,57 +575,39 @@ __global__ __launch_bounds__(256, 8) void k_seeds(const QueryArgs a, const SeedB
         for (; ls < ls_end; ++ls) {
             spans[2 * ls] = spans[2 * ls + 1] = 0;
             rng[2 * ls] = rng[2 * ls + 1] = 0;
-            if (loc) recs[ls] = SearchRec<P>{P(0), P(0), 0ull};
+            if (loc) zero_record<P>(recs, ls);
         }
     }
-    if (loc) {
-        __syncthreads();
-        const uint64_t tile = (uint64_t)blockIdx.x * ms + threadIdx.x;
-        if (threadIdx.x < ms && tile < G) B.tiles[tile] = s_tile[threadIdx.x];
-    }
+    if (loc) store_tile_counts(B.tiles, s_tile, ms, G);
 }
 
-// ------------------------------------------------ k_approx (k-mismatch search)
-// One lane per pattern, k_seeds' shape, the pattern staged once: approx_search
-// hands the lane its pattern's variants in the contract's order, and the lane
-// stores the first max_hits of them — pattern i owns slots [i max_hits, (i+1)
-// max_hits): mm, the substitutions (3 pairs of position, symbol) and (lo, hi)
-// per slot, the unused pairs and slots zero — and ends the search at the
-// (max_hits + 1)-th (more = 1).  With B.tiles every slot also gets k_emit's
-// record — {lo, count, 0}, the count 0 unless the hit reports (count <=
-// max_occ; unused slots: zeros); one row under a full SA is located here by
-// that one read, any other is left to k_emit's walk (no sampled row is tracked
-// across the backtracking) — and the workgroup, whose slots are exactly
-// max_hits whole 256-slot tiles of k_emit, adds each reporting hit's count to
-// its tile's in LDS and writes the tile counts, as k_seeds does.
+// k_approx: approx_search hands the lane its pattern's variants in the
+// contract's order, and the lane stores the first max_hits of them — mm, the
+// substitutions (3 pairs of position, symbol, the unused pairs zero) and (lo,
+// hi) per slot — and ends the search at the (max_hits + 1)-th (more = 1).  No
+// sampled row is tracked across the backtracking.
 template <typename P, int N, int VB, int REC>
 __global__ __launch_bounds__(256, 5) void k_approx(const QueryArgs a, const ApproxBatch B, uint32_t stage_bytes) {
     __shared__ Tables<P> s;
     FMX_DYN_LDS(s_pat);  // stage_bytes, then the k-mer table (dynamic)
     __shared__ unsigned long long s_tile[kMaxHits];
     stage_tables(a, s, s_pat + stage_bytes);
-    if (threadIdx.x < kMaxHits) s_tile[threadIdx.x] = 0;  // (visible after stage_patterns' barrier)
-    const uint8_t *__restrict__ bytes = B.bytes;
+    if (threadIdx.x < kMaxHits) s_tile[threadIdx.x] = 0;  // (visible after lane_pattern's barrier)
     const uint64_t npat = B.npat, first = (uint64_t)blockIdx.x * 256u;
-    const bool rev = B.rev != 0;
-    uint64_t beg, end, b0, b1;
-    const bool staged =
-        stage_patterns(s, s_pat, bytes, B.offs, npat, first, rev, stage_bytes, B.stride, a.status, beg, end, b0, b1);
-    __syncthreads();
-    const uint64_t i = first + threadIdx.x;
+    bool has, staged;
+    const PatView pv = lane_pattern(s, s_pat, B.bytes, B.offs, npat, first, B.rev != 0, stage_bytes, B.stride, a.status,
+                                    has, staged);
     const uint32_t mh = B.max_hits;
     const bool loc = B.tiles != nullptr;         // (workgroup-uniform)
     const uint64_t G = (npat * mh + 255) / 256;  // the batch's 256-slot tiles
-    if (i < npat) {
-        const PatView pv = pattern_view(s, s_pat, staged, bytes, beg, end, b0, b1, rev);
-        // the outputs are addressed from the workgroup's first slot (uniform) by a 32-bit slot number
+    if (has) {
         const uint64_t slot0 = first * mh;
         uint32_t *__restrict__ mm = B.out_mm + slot0;
         uint32_t *__restrict__ subs = B.out_subs + 6 * slot0;
         P *__restrict__ rng = reinterpret_cast<P *>(B.out_rng) + 2 * slot0;
         SearchRec<P> *__restrict__ recs = nullptr;
-        if (loc) recs = reinterpret_cast<SearchRec<P> *>(B.tiles + 2 * G) + slot0;
-        uint32_t ls = threadIdx.x * mh;  // hit j's slot in the workgroup: tile ls >> 8 of its max_hits
+        if (loc) recs = slot_records<P>(B.tiles, G, slot0);
+        uint32_t ls = threadIdx.x * mh;  // hit j's slot in the workgroup
         const uint32_t ls_end = ls + mh;
         uint32_t more = 0;
         approx_search<P, N, VB, REC>(
@@ -584,15 +627,7 @@ __global__ __launch_bounds__(256, 5) void k_approx(const QueryArgs a, const Appr
                 sb[5] = d > 2 ? f2.sym() : 0u;
                 rng[2 * ls] = lo;
                 rng[2 * ls + 1] = hi;
-                if (loc) {
-                    const uint64_t cnt = (uint64_t)(hi - lo) <= B.max_occ ? (uint64_t)(hi - lo) : 0;
-                    if (cnt == 1 && a.safull != nullptr)  // (walk_row's one read)
-                        recs[ls] = SearchRec<P>{reinterpret_cast<const P *>(a.safull)[(uint64_t)lo * a.sa_stride], P(1),
-                                                1ull};
-                    else
-                        recs[ls] = SearchRec<P>{lo, (P)cnt, 0ull};
-                    if (cnt) atomicAdd(&s_tile[ls >> 8], (unsigned long long)cnt);
-                }
+                if (loc) slot_record<P>(a, recs, s_tile, ls, lo, slot_count<P>(lo, hi, B.max_occ));
                 ++ls;
                 return false;
             });
@@ -604,14 +639,10 @@ __global__ __launch_bounds__(256, 5) void k_approx(const QueryArgs a, const Appr
 #pragma unroll
             for (int u = 0; u < 6; ++u) sb[u] = 0;
             rng[2 * ls] = rng[2 * ls + 1] = 0;
-            if (loc) recs[ls] = SearchRec<P>{P(0), P(0), 0ull};
+            if (loc) zero_record<P>(recs, ls);
         }
     }
-    if (loc) {
-        __syncthreads();
-        const uint64_t tile = (uint64_t)blockIdx.x * mh + threadIdx.x;
-        if (threadIdx.x < mh && tile < G) B.tiles[tile] = s_tile[threadIdx.x];
-    }
+    if (loc) store_tile_counts(B.tiles, s_tile, mh, G);
 }
 
 // ------------------------------------------- k_locate (search + emit, fused)

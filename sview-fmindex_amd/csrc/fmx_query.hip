@@ -684,97 +684,88 @@ hipError_t launch_locate(const fmx_index *ix, const uint8_t *d_bytes, const uint
     group_reset(grp);
     grp.tile_begin[0] = 0;
     grp.b[0] = LocateBatch{d_bytes, d_offsets, n, d_counts, d_loc_offsets, d_locs, cap, d_needed, d_tiles,
-                           (flags & FMX_PATTERN_REVERSED) ? 1u : 0u, flags >> 16};
+                           flags_rev(flags), flags_stride(flags)};
     grp.n = 1;
     return launch_split(ix, qa, grp, (uint32_t)((n + 255) / 256), stage_bytes_for(flags), stream);
 }
 
-// Longest-suffix match, in launch order: k_match, then — when locations are
-// asked for — the locate's own last kernels over the records it left.
-hipError_t launch_match(const fmx_index *ix, const uint8_t *d_bytes, const uint64_t *d_offsets, uint64_t n,
-                        uint32_t flags, uint32_t min_len, uint64_t max_occ, uint32_t *d_lens, void *d_ranges,
-                        uint64_t *d_loc_offsets, void *d_locs, uint64_t cap, uint64_t *d_needed, uint64_t *d_tiles,
-                        uint64_t tiles_cap, uint32_t *status, hipStream_t stream) {
-    if (n == 0) return hipSuccess;
-    QueryArgs qa = ix->qa;
-    qa.status = status;
-    const uint64_t tiles = (n + 255) / 256;
-    const bool loc = d_loc_offsets != nullptr;
-    if (tiles > 0x7FFFFFFFull || (loc && (tiles > tiles_cap || !d_tiles))) return hipErrorInvalidValue;
-    const uint32_t rev = (flags & FMX_PATTERN_REVERSED) ? 1u : 0u, stride = flags >> 16;
-    const MatchBatch mb{d_bytes, d_offsets, n, d_lens, d_ranges, loc ? d_tiles : nullptr, max_occ, min_len, rev, stride};
-    const Disp d = dispatch(ix);
-    hipError_t e = d.ops->match(qa, d.vb, d.rec, mb, (uint32_t)tiles, stage_bytes_for(flags), stream);
-    if (e != hipSuccess || !loc) return e;
-    // one batch in launch order for k_scan / k_emit (neither reads the patterns)
+// The slot queries (fmx_internal.hpp, LocOut): the query's own kernel, then —
+// when locations are asked for — the locate's last kernels over the records it
+// left, one "pattern" per slot.
+
+// Whether a launch takes `slots` slots: their 256-slot tiles, and with locations the workspace's room for them
+static bool slots_ok(uint64_t slots, const LocOut &out) {
+    const uint64_t tiles = (slots + 255) / 256;
+    return tiles <= 0x7FFFFFFFull && (!out.loc_offsets || (tiles <= out.tiles_cap && out.tiles));
+}
+
+// One batch of `slots` records in launch order for k_scan / k_emit (neither reads the patterns).
+static hipError_t emit_slots(const fmx_index *ix, const QueryArgs &qa, uint64_t slots, const LocOut &out,
+                             hipStream_t stream) {
     LocateGroup grp;
     group_reset(grp);
     grp.tile_begin[0] = 0;
-    grp.b[0] = LocateBatch{d_bytes, d_offsets, n, nullptr, d_loc_offsets, d_locs, cap, d_needed, d_tiles, rev, stride};
+    grp.b[0] = LocateBatch{nullptr, nullptr, slots, nullptr, out.loc_offsets, out.locs, out.cap, out.needed, out.tiles,
+                           0u, 0u};
     grp.n = 1;
-    return launch_emit(ix, qa, grp, (uint32_t)tiles, 0u, stream);
+    return launch_emit(ix, qa, grp, (uint32_t)((slots + 255) / 256), 0u, stream);
 }
 
-// Greedy seed chains, in launch order: k_seeds (a workgroup per 256
-// patterns), then — when locations are asked for — the locate's own last
-// kernels over the n * max_seeds slots' records, one "pattern" per slot.
+// Longest-suffix match: k_match, a slot per pattern.
+hipError_t launch_match(const fmx_index *ix, const uint8_t *d_bytes, const uint64_t *d_offsets, uint64_t n,
+                        uint32_t flags, uint32_t min_len, uint64_t max_occ, uint32_t *d_lens, void *d_ranges,
+                        const LocOut &out, uint32_t *status, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    QueryArgs qa = ix->qa;
+    qa.status = status;
+    if (!slots_ok(n, out)) return hipErrorInvalidValue;
+    const bool loc = out.loc_offsets != nullptr;
+    const MatchBatch mb{d_bytes, d_offsets, n, d_lens, d_ranges, loc ? out.tiles : nullptr, max_occ, min_len,
+                        flags_rev(flags), flags_stride(flags)};
+    const Disp d = dispatch(ix);
+    const hipError_t e = d.ops->match(qa, d.vb, d.rec, mb, (uint32_t)((n + 255) / 256), stage_bytes_for(flags), stream);
+    return e != hipSuccess || !loc ? e : emit_slots(ix, qa, n, out, stream);
+}
+
+// Greedy seed chains: k_seeds (a workgroup per 256 patterns), max_seeds slots per pattern.
 hipError_t launch_seeds(const fmx_index *ix, const uint8_t *d_bytes, const uint64_t *d_offsets, uint64_t n,
                         uint32_t flags, uint32_t max_seeds, uint32_t min_len, uint32_t skip, uint64_t max_occ,
-                        uint32_t *d_nseeds, uint32_t *d_rest, uint32_t *d_spans, void *d_ranges,
-                        uint64_t *d_loc_offsets, void *d_locs, uint64_t cap, uint64_t *d_needed, uint64_t *d_tiles,
-                        uint64_t tiles_cap, uint32_t *status, hipStream_t stream) {
+                        uint32_t *d_nseeds, uint32_t *d_rest, uint32_t *d_spans, void *d_ranges, const LocOut &out,
+                        uint32_t *status, hipStream_t stream) {
     if (n == 0) return hipSuccess;
     if (max_seeds == 0 || max_seeds > kMaxSeeds || n > ~0ull / max_seeds) return hipErrorInvalidValue;
     QueryArgs qa = ix->qa;
     qa.status = status;
-    const uint64_t slots = n * max_seeds, tiles = (slots + 255) / 256, wgs = (n + 255) / 256;
-    const bool loc = d_loc_offsets != nullptr;
-    if (tiles > 0x7FFFFFFFull || (loc && (tiles > tiles_cap || !d_tiles))) return hipErrorInvalidValue;
-    const uint32_t rev = (flags & FMX_PATTERN_REVERSED) ? 1u : 0u, stride = flags >> 16;
-    const SeedBatch sb{d_bytes, d_offsets, n,        d_nseeds, d_rest, d_spans, d_ranges, loc ? d_tiles : nullptr,
-                       max_occ, max_seeds, min_len, skip,     rev,    stride};
+    const uint64_t slots = n * max_seeds, wgs = (n + 255) / 256;
+    if (!slots_ok(slots, out)) return hipErrorInvalidValue;
+    const bool loc = out.loc_offsets != nullptr;
+    const SeedBatch sb{d_bytes, d_offsets, n,        d_nseeds, d_rest,           d_spans,
+                       d_ranges, loc ? out.tiles : nullptr,    max_occ, max_seeds, min_len, skip,
+                       flags_rev(flags), flags_stride(flags)};
     const Disp d = dispatch(ix);
-    hipError_t e = d.ops->seeds(qa, d.vb, d.rec, sb, (uint32_t)wgs, stage_bytes_for(flags), stream);
-    if (e != hipSuccess || !loc) return e;
-    // one batch of `slots` records in launch order for k_scan / k_emit (neither reads the patterns)
-    LocateGroup grp;
-    group_reset(grp);
-    grp.tile_begin[0] = 0;
-    grp.b[0] = LocateBatch{nullptr, nullptr, slots, nullptr, d_loc_offsets, d_locs, cap, d_needed, d_tiles, 0u, 0u};
-    grp.n = 1;
-    return launch_emit(ix, qa, grp, (uint32_t)tiles, 0u, stream);
+    const hipError_t e = d.ops->seeds(qa, d.vb, d.rec, sb, (uint32_t)wgs, stage_bytes_for(flags), stream);
+    return e != hipSuccess || !loc ? e : emit_slots(ix, qa, slots, out, stream);
 }
 
-// k-mismatch search, in launch order: k_approx (a workgroup per 256 patterns),
-// then — when locations are asked for — the locate's own last kernels over the
-// n * max_hits slots' records, one "pattern" per slot (as launch_seeds).
+// k-mismatch search: k_approx (a workgroup per 256 patterns), max_hits slots per pattern.
 hipError_t launch_approx(const fmx_index *ix, const uint8_t *d_bytes, const uint64_t *d_offsets, uint64_t n,
                          uint32_t flags, uint32_t max_mm, uint32_t max_hits, uint32_t mode, uint64_t max_occ,
                          uint32_t *d_nhits, uint32_t *d_more, uint32_t *d_mm, uint32_t *d_subs, void *d_ranges,
-                         uint64_t *d_loc_offsets, void *d_locs, uint64_t cap, uint64_t *d_needed, uint64_t *d_tiles,
-                         uint64_t tiles_cap, uint32_t *status, hipStream_t stream) {
+                         const LocOut &out, uint32_t *status, hipStream_t stream) {
     if (n == 0) return hipSuccess;
     if (max_mm > kMaxMismatch || max_hits == 0 || max_hits > kMaxHits || n > ~0ull / max_hits)
         return hipErrorInvalidValue;
     QueryArgs qa = ix->qa;
     qa.status = status;
-    const uint64_t slots = n * max_hits, tiles = (slots + 255) / 256, wgs = (n + 255) / 256;
-    const bool loc = d_loc_offsets != nullptr;
-    if (tiles > 0x7FFFFFFFull || (loc && (tiles > tiles_cap || !d_tiles))) return hipErrorInvalidValue;
-    const uint32_t rev = (flags & FMX_PATTERN_REVERSED) ? 1u : 0u, stride = flags >> 16;
-    const ApproxBatch ab{d_bytes, d_offsets, n,      d_nhits, d_more,   d_mm,
-                         d_subs,  d_ranges,  loc ? d_tiles : nullptr,  max_occ, max_mm, max_hits,
-                         (mode & FMX_APPROX_BEST) ? 1u : 0u, rev, stride};
+    const uint64_t slots = n * max_hits, wgs = (n + 255) / 256;
+    if (!slots_ok(slots, out)) return hipErrorInvalidValue;
+    const bool loc = out.loc_offsets != nullptr;
+    const ApproxBatch ab{d_bytes, d_offsets, n,       d_nhits, d_more,   d_mm,
+                         d_subs,  d_ranges,  loc ? out.tiles : nullptr,  max_occ, max_mm, max_hits,
+                         (mode & FMX_APPROX_BEST) ? 1u : 0u, flags_rev(flags), flags_stride(flags)};
     const Disp d = dispatch(ix);
-    hipError_t e = d.ops->approx(qa, d.vb, d.rec, ab, (uint32_t)wgs, stage_bytes_for(flags), stream);
-    if (e != hipSuccess || !loc) return e;
-    // one batch of `slots` records in launch order for k_scan / k_emit (neither reads the patterns)
-    LocateGroup grp;
-    group_reset(grp);
-    grp.tile_begin[0] = 0;
-    grp.b[0] = LocateBatch{nullptr, nullptr, slots, nullptr, d_loc_offsets, d_locs, cap, d_needed, d_tiles, 0u, 0u};
-    grp.n = 1;
-    return launch_emit(ix, qa, grp, (uint32_t)tiles, 0u, stream);
+    const hipError_t e = d.ops->approx(qa, d.vb, d.rec, ab, (uint32_t)wgs, stage_bytes_for(flags), stream);
+    return e != hipSuccess || !loc ? e : emit_slots(ix, qa, slots, out, stream);
 }
 
 static hipError_t check_group(const LocateGroup &grp, uint64_t *tiles) {

@@ -7,40 +7,16 @@ its exact size and weakest alignment out of one 0xA5-filled array
 workspace, no location buffers), and the unstaged path (a 1 KB stage): guards
 and inputs untouched, every output the expected value,
 d_locs[min(cap, total):cap] unwritten."""
-import ctypes as C
-import os
-import subprocess
 
 import pytest
 
 import _approx_guard_cases as AG
 from _approx_cases import case_for, open_index
 from _guard_cases import HostMem
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-SIMT_DIR = os.path.join(HERE, "simt")
-SIMT_LIB = os.path.join(SIMT_DIR, "libfmx_simt.so")
+from _simt import simt_fixture
 
 
-@pytest.fixture(scope="module")
-def simt(pkg):
-    subprocess.check_call(["make", "-s", "-j", str(min(8, os.cpu_count() or 1)), "-C", SIMT_DIR])
-    n = pkg._native
-    L = C.CDLL(SIMT_LIB)
-    for name, (res, args) in n.SIGNATURES.items():
-        f = getattr(L, name)
-        f.restype = res
-        f.argtypes = args
-    L.simt_config.argtypes = [C.c_uint64, C.c_double]
-    L.simt_config.restype = None
-    L.simt_defer.argtypes = [C.c_int, C.c_double]
-    L.simt_defer.restype = None
-    # deferred streams, as tests/test_simt.py: queued work runs at a random later host call
-    L.simt_defer(1, 0.25)
-    saved = n._lib
-    n._lib = L
-    yield L
-    n._lib = saved
+simt = simt_fixture(launch_order=False)
 
 
 @pytest.mark.parametrize("skew", AG.SKEWS)

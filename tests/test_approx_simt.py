@@ -7,8 +7,6 @@ pattern 85's slots straddle the first tile boundary), forward and reversed,
 FMX_APPROX_BEST; max_occ; a two-letter text (more than 32 variants per pattern);
 ranges only; capacity; PassThrough bytes; the device call; argument checks."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,39 +14,10 @@ import pytest
 from _approx_cases import (BATCH_SIZES, assert_classes, batch, case_for, check_approx, compare, cross_check,
                            cross_check_exact, expected_arrays, open_index, variants)
 from _match_cases import ABSENT
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-SIMT_DIR = os.path.join(HERE, "simt")
-SIMT_LIB = os.path.join(SIMT_DIR, "libfmx_simt.so")
+from _simt import simt_fixture
 
 
-@pytest.fixture(scope="module")
-def simt(pkg):
-    subprocess.check_call(["make", "-s", "-j", str(min(8, os.cpu_count() or 1)), "-C", SIMT_DIR])
-    n = pkg._native
-    L = C.CDLL(SIMT_LIB)
-    for name, (res, args) in n.SIGNATURES.items():
-        f = getattr(L, name)
-        f.restype = res
-        f.argtypes = args
-    L.simt_config.argtypes = [C.c_uint64, C.c_double]
-    L.simt_config.restype = None
-    L.simt_defer.argtypes = [C.c_int, C.c_double]
-    L.simt_defer.restype = None
-    # deferred streams, as tests/test_simt.py: queued work runs at a random later host call
-    L.simt_defer(1, 0.25)
-    # (the locate_batch calls compared with below: workgroups run one at a time here, so no fused launch)
-    saved_env = {k: os.environ.get(k) for k in ("FMX_FUSED", "FMX_EMIT_CHAIN")}
-    os.environ["FMX_FUSED"] = os.environ["FMX_EMIT_CHAIN"] = "0"
-    saved = n._lib
-    n._lib = L
-    yield L
-    n._lib = saved
-    for k, v in saved_env.items():
-        if v is None:
-            os.environ.pop(k, None)
-        else:
-            os.environ[k] = v
+simt = simt_fixture(launch_order=True)
 
 
 # (P bytes, planes, vector bits): the layouts of tests/test_seeds_simt.py

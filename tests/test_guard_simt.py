@@ -16,42 +16,17 @@ under two emulator schedules; layouts (4,3,64), (8,3,128) and (4,5,64) with 21 s
 load options 0 and 1, and every derived structure (63) for (4,3,64) in launch
 order (a grouped launch needs the faithful index).  Host calls: the capacity
 contract of fmx_locate_batch and fmx_match_batch."""
-import ctypes as C
 import itertools
-import os
-import subprocess
 
 import pytest
 
 import _guard_cases as G
+from _simt import simt_fixture
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SIMT_DIR = os.path.join(HERE, "simt")
-SIMT_LIB = os.path.join(SIMT_DIR, "libfmx_simt.so")
 SEEDS = (0, 1)
 
 
-@pytest.fixture(scope="module")
-def simt(pkg):
-    subprocess.check_call(["make", "-s", "-j", str(min(8, os.cpu_count() or 1)), "-C", SIMT_DIR])
-    n = pkg._native
-    L = C.CDLL(SIMT_LIB)
-    for name, (res, args) in n.SIGNATURES.items():
-        f = getattr(L, name)
-        f.restype = res
-        f.argtypes = args
-    L.simt_config.argtypes = [C.c_uint64, C.c_double]
-    L.simt_config.restype = None
-    L.simt_defer.argtypes = [C.c_int, C.c_double]
-    L.simt_defer.restype = None
-    L.simt_block_order.argtypes = [C.c_int]
-    L.simt_block_order.restype = None
-    # deferred streams, as tests/test_simt.py: queued work runs at a random later host call
-    L.simt_defer(1, 0.25)
-    saved = n._lib
-    n._lib = L
-    yield L
-    n._lib = saved
+simt = simt_fixture(launch_order=False)
 
 
 @pytest.fixture

@@ -11,46 +11,15 @@ start; unique substrings behind a wrong symbol (sampled-row rollback); a
 two-letter text (hundreds of rows per match); capacity; min_len / max_occ;
 ranges only; PassThrough bytes >= symbol_count; the device call."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from _match_cases import ABSENT, BATCH_SIZES, Case, check_match
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-SIMT_DIR = os.path.join(HERE, "simt")
-SIMT_LIB = os.path.join(SIMT_DIR, "libfmx_simt.so")
+from _simt import simt_fixture
 
 
-@pytest.fixture(scope="module")
-def simt(pkg):
-    subprocess.check_call(["make", "-s", "-j", str(min(8, os.cpu_count() or 1)), "-C", SIMT_DIR])
-    n = pkg._native
-    L = C.CDLL(SIMT_LIB)
-    for name, (res, args) in n.SIGNATURES.items():
-        f = getattr(L, name)
-        f.restype = res
-        f.argtypes = args
-    L.simt_config.argtypes = [C.c_uint64, C.c_double]
-    L.simt_config.restype = None
-    L.simt_defer.argtypes = [C.c_int, C.c_double]
-    L.simt_defer.restype = None
-    # deferred streams, as tests/test_simt.py: queued work runs at a random later host call
-    L.simt_defer(1, 0.25)
-    # (the locate_batch calls compared with below: workgroups run one at a time here, so no fused launch)
-    saved_env = {k: os.environ.get(k) for k in ("FMX_FUSED", "FMX_EMIT_CHAIN")}
-    os.environ["FMX_FUSED"] = os.environ["FMX_EMIT_CHAIN"] = "0"
-    saved = n._lib
-    n._lib = L
-    yield L
-    n._lib = saved
-    for k, v in saved_env.items():
-        if v is None:
-            os.environ.pop(k, None)
-        else:
-            os.environ[k] = v
+simt = simt_fixture(launch_order=True)
 
 
 def pos_of(pkg, pb):

@@ -18,58 +18,15 @@ grouped launches on one workspace), on every layout, and on multi-batch
 launches reusing workspaces."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from _util import ALL_LAYOUTS, rand_chr_list, rand_pattern, rand_text, table_from_symbols
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-SIMT_DIR = os.path.join(HERE, "simt")
-SIMT_LIB = os.path.join(SIMT_DIR, "libfmx_simt.so")
+from _simt import simt_fixture
 
 
-@pytest.fixture(scope="module")
-def simt(pkg):
-    subprocess.check_call(["make", "-s", "-j", str(min(8, os.cpu_count() or 1)), "-C", SIMT_DIR])
-    n = pkg._native
-    L = C.CDLL(SIMT_LIB)
-    for name, (res, args) in n.SIGNATURES.items():
-        f = getattr(L, name)
-        f.restype = res
-        f.argtypes = args
-    L.simt_config.argtypes = [C.c_uint64, C.c_double]
-    L.simt_config.restype = None
-    L.simt_stats.argtypes = [C.POINTER(C.c_uint64)] * 3
-    L.simt_stats.restype = None
-    L.simt_memset_fault.argtypes = [C.c_uint64, C.POINTER(C.c_uint32), C.c_uint64]
-    L.simt_memset_fault.restype = None
-    L.simt_defer.argtypes = [C.c_int, C.c_double]
-    L.simt_defer.restype = None
-    L.simt_selftest_defer.argtypes = []
-    L.simt_selftest_defer.restype = C.c_int
-    L.simt_block_order.argtypes = [C.c_int]
-    L.simt_block_order.restype = None
-    # deferred streams for every test here: work queued on a stream runs at a
-    # random later host call or when the host synchronises, copies read and
-    # write host memory when they run (simt_rt.cpp)
-    L.simt_defer(1, 0.25)
-    # workgroups run one at a time in a shuffled order here, so the fused
-    # launch (k_locate: a workgroup waits for its batch's earlier tiles) is off
-    # by default and tested with index-ordered workgroups (fused fixture)
-    # (and k_emit_chain, which ends grouped launches the same way)
-    saved_env = {k: os.environ.get(k) for k in ("FMX_FUSED", "FMX_EMIT_CHAIN")}
-    os.environ["FMX_FUSED"] = os.environ["FMX_EMIT_CHAIN"] = "0"
-    saved = n._lib
-    n._lib = L
-    yield L
-    n._lib = saved
-    for k, v in saved_env.items():
-        if v is None:
-            os.environ.pop(k, None)
-        else:
-            os.environ[k] = v
+simt = simt_fixture(launch_order=True)
 
 
 def pos_of(pkg, pb):
