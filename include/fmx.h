@@ -78,6 +78,12 @@ typedef struct fmx_layout {
  * bytes from d_bytes, which must be that large.  The host-buffer calls set
  * the hint themselves when every pattern has the same length. */
 #define FMX_HINT_FIXED_LEN(m) ((((uint32_t)(m)) & 0xffffu) << 16)
+/* Strand flags of the slot queries (fmx_match_batch, fmx_seeds_batch,
+ * fmx_approx_batch and their _async forms; "Both strands" below).  They need a
+ * complement map (fmx_set_complement), exclude each other, and are FMX_E_ARG
+ * in every count and locate call. */
+#define FMX_PATTERN_REVCOMP 4u /* each pattern is searched as its reverse complement only       */
+#define FMX_BOTH_STRANDS 8u    /* each pattern is searched as given and as its reverse complement */
 
 /* Load options: device-side structures derived from the blob at load time.
  * Results are identical with any combination; they trade HBM for fewer
@@ -206,6 +212,41 @@ const uint8_t *fmx_blob(const fmx_index *ix, uint64_t *len);
 
 fmx_status fmx_info(const fmx_index *ix, fmx_index_info *out);
 
+/* Both strands.  The complement map of the strand flags: map[b] is the
+ * complement of input byte b (256 bytes, byte to byte; NULL removes the map).
+ * Any map is legal: it need not be an involution, and bytes outside the
+ * alphabet map wherever the caller says.  The index keeps the 256-byte device
+ * table enc_rc[b] = enc[map[b]] (enc: the index's encoding table; PassThrough:
+ * the identity, so enc_rc = map and a map[b] >= symbol_count ends a match as
+ * such a byte of a pattern does).  Synchronous; applies to launches queued
+ * after it returns.  Calling it while strand launches of this index are in
+ * flight leaves it undefined which of the two tables each of them uses — never
+ * a fault: the table is always 256 entries indexed by a byte.
+ * fmx_get_complement copies the map that was set to map_out (256 bytes);
+ * FMX_E_ARG when none is set.
+ *
+ * The contract, with pattern i in logical order p[0..m) (FMX_PATTERN_REVERSED
+ * still only says how its bytes arrive) and rc(p)[j] = map[p[m-1-j]], j in
+ * 0..m: a call with FMX_PATTERN_REVCOMP returns exactly what the same call
+ * without the flag returns for the batch rc(p_0), ..., rc(p_{n-1}); a call
+ * with FMX_BOTH_STRANDS returns exactly what it returns for the 2n-pattern
+ * batch p_0, rc(p_0), p_1, rc(p_1), ...: virtual pattern v = 2 i + s is strand
+ * s of read i.  Under FMX_BOTH_STRANDS every per-pattern output array has 2n
+ * entries, every per-slot array 2n * per (per = 1, max_seeds or max_hits),
+ * loc_offsets 2n * per + 1, the workspace is fmx_locate_workspace_size(2n *
+ * per) bytes, and the slot limit and the timer units count 2n patterns.
+ * Positions reported for strand 1 (seed spans, approx substitutions) are in
+ * rc(p)'s own coordinates: a seed covering rc(p)[e-L..e) is p[m-e..m-e+L) of
+ * the read.  Ranges-only mode, the capacity contract, min_len / max_occ /
+ * FMX_APPROX_BEST hold unchanged on the virtual batch; FMX_HINT_FIXED_LEN and
+ * the offsets are the n reads' (a disagreement is still FMX_E_ARG), and the
+ * reads' bytes are uploaded and read once.  FMX_E_ARG: both flags together,
+ * either flag on an index without a map, either flag in fmx_count_batch,
+ * fmx_locate_batch, their _async forms, fmx_locate_jobs_async or
+ * fmx_locate_group_async. */
+fmx_status fmx_set_complement(fmx_index *ix, const uint8_t *map);
+fmx_status fmx_get_complement(const fmx_index *ix, uint8_t *map_out);
+
 /* ---------------------------------------------- queries on host buffers
  * Synchronous.  Patterns are ragged: pattern i is bytes[offsets[i] .. offsets[i+1]). */
 
@@ -255,6 +296,16 @@ fmx_status fmx_locate_batch(fmx_index *ix, const uint8_t *bytes, const uint64_t 
  *    bytes (fmx_seeds_batch_async: of n_patterns * max_seeds, and
  *    fmx_approx_batch_async: of n_patterns * max_hits, one "pattern" per
  *    slot); a launch may write any of it and nothing outside it.
+ *  - FMX_BOTH_STRANDS: d_bytes and d_offsets are the n_patterns reads' (read
+ *    by the rule above, once), and every size above that is counted in
+ *    patterns or slots is taken with 2 n_patterns for n_patterns: 2 n lens
+ *    and 4 n range words for a match, 2 n counts (d_nseeds, d_rest, d_nhits,
+ *    d_more) and S = 2 n * per slots for seeds and approx, S + 1 location
+ *    offsets, a workspace of fmx_locate_workspace_size(S) bytes.  Exactly
+ *    that size, no byte outside it touched.  To stage both strands' copies
+ *    of a tile (128 reads) FMX_HINT_STAGE_KB must cover twice the bytes the
+ *    tile's reads span; a tile that does not fit is read from HBM.
+ *    FMX_PATTERN_REVCOMP changes no size.
  *  - cap = 0 with d_locs = NULL sizes an output: the offsets, the counts and
  *    *d_needed are written, no location is. */
 
@@ -369,7 +420,10 @@ fmx_status fmx_locate_group_async(fmx_index *ix, const fmx_locate_job *jobs, uin
  * either way), and the device call's workspace has the size of
  * fmx_locate_workspace_size and the same 16-B alignment rule.  The host call
  * sets the staging and fixed-length hints itself.  A match runs in launch
- * order: k_match, then the locate's k_emit.  Timer: "match". */
+ * order: k_match, then the locate's k_emit.  Timer: "match".
+ * FMX_PATTERN_REVCOMP / FMX_BOTH_STRANDS (here, in fmx_seeds_batch and in
+ * fmx_approx_batch): "Both strands" above — the same call on rc(p_i), or on
+ * the 2n patterns p_0, rc(p_0), p_1, ..., with every output shaped for them. */
 fmx_status fmx_match_batch(fmx_index *ix, const uint8_t *bytes, const uint64_t *offsets,
                            uint64_t n_patterns, uint32_t flags, uint32_t min_len, uint64_t max_occ,
                            uint32_t *out_lens, void *out_ranges, uint64_t *out_loc_offsets,

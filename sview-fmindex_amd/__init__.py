@@ -44,7 +44,7 @@ from . import distributed  # noqa: F401  (multi-GPU helpers)
 
 __all__ = ["FmIndex", "FmIndexBuilder", "Position", "u32", "u64", "Vector", "blocks",
            "text_encoders", "build_config", "LoadError", "BuildError", "FmxError",
-           "aligned_buffer", "pack_patterns"]
+           "aligned_buffer", "pack_patterns", "complement_map"]
 
 
 # ------------------------------------------------------------------ errors
@@ -341,6 +341,26 @@ def _flags(reversed: bool, long_patterns: bool, stage_kb: int = 0, fixed_len: in
             | ((int(stage_kb) & 0xFF) << 8) | (int(fixed_len) << 16))
 
 
+def _strand_flags(strands: str) -> int:
+    """strands = "forward" | "reverse" | "both": no flag, FMX_PATTERN_REVCOMP or
+    FMX_BOTH_STRANDS (the last two need FmIndex.set_complement)."""
+    try:
+        return {"forward": 0, "reverse": _n.FMX_PATTERN_REVCOMP, "both": _n.FMX_BOTH_STRANDS}[strands]
+    except KeyError:
+        raise ValueError('strands must be "forward", "reverse" or "both"') from None
+
+
+def complement_map(pairs: Iterable[Tuple[bytes, bytes]]) -> bytes:
+    """A 256-byte complement map that swaps the two bytes of each pair and
+    leaves every other byte as it is: complement_map([(b"A", b"T"), (b"C",
+    b"G")]) for upper-case DNA."""
+    m = bytearray(range(256))
+    for a, b in pairs:
+        (x,), (y,) = bytes(a), bytes(b)
+        m[x], m[y] = y, x
+    return bytes(m)
+
+
 def _ptr(a: Optional[np.ndarray]):
     return None if a is None else C.c_void_p(a.ctypes.data)
 
@@ -352,20 +372,23 @@ def _vp(x: int):
 
 def _host_query(name: str, h, dt, patterns, reversed: bool, params: Optional[tuple] = None,
                 max_occ: Optional[int] = None, outs=lambda n: (), per: int = 1, locate: bool = True,
-                cap: int = 1 << 16):
+                cap: int = 1 << 16, strands: str = "forward"):
     """One host-buffer query `name(h, bytes, offsets, n, flags, *params,
     max_occ, *outs(n), loc_offsets, locations, cap, &needed)` (params None: a
     call without them and without max_occ): the patterns packed, max_occ None
     as no bound, and — with `locate` — the locations of n * per slots, their
     buffer grown to `needed` and the call repeated once on FMX_E_CAPACITY.
     Returns (n, outputs, loc_offsets uint64[n * per + 1], locations[:needed]),
-    the last two None without `locate`."""
+    the last two None without `locate`; under strands="both" the returned n
+    and every output count the 2n virtual patterns (read i's strand s: 2 i +
+    s)."""
     data, offsets = patterns if isinstance(patterns, tuple) else pack_patterns(patterns)
-    n = offsets.size - 1
+    reads = offsets.size - 1
+    n = 2 * reads if strands == "both" else reads
     out = outs(n)
-    flags = _n.FMX_PATTERN_REVERSED if reversed else 0
+    flags = (_n.FMX_PATTERN_REVERSED if reversed else 0) | _strand_flags(strands)
     mid = () if params is None else params + ((1 << 64) - 1 if max_occ is None else int(max_occ),)
-    head = (h, _ptr(data) if data.size else None, _ptr(offsets), n, flags) + mid + tuple(_ptr(o) for o in out)
+    head = (h, _ptr(data) if data.size else None, _ptr(offsets), reads, flags) + mid + tuple(_ptr(o) for o in out)
     fn = getattr(_n.lib(), name)
     needed = C.c_uint64()
     if not locate:
@@ -523,6 +546,27 @@ class FmIndex:
         _check(_n.lib().fmx_info(self._h, C.byref(i)))
         return {f: getattr(i, f) for f, _ in i._fields_}
 
+    # -- the complement map of strands="reverse" / "both" ------------------
+    def set_complement(self, map: Optional[bytes]) -> None:
+        """fmx_set_complement: `map` is 256 bytes, byte -> complement byte (see
+        complement_map), or None to remove it.  Not to be called while strand
+        queries of this index are in flight."""
+        if map is not None:
+            map = bytes(map)
+            if len(map) != 256:
+                raise ValueError("a complement map is 256 bytes")
+        _check(_n.lib().fmx_set_complement(self._h, map), "fmx_set_complement")
+
+    @property
+    def complement(self) -> Optional[bytes]:
+        """The map that was set, or None."""
+        buf = C.create_string_buffer(256)
+        st = _n.lib().fmx_get_complement(self._h, buf)
+        if st == _n.FMX_E_ARG:
+            return None
+        _check(st, "fmx_get_complement")
+        return buf.raw
+
     # -- single-pattern API (the reference's own) -----------------------
     def count(self, pattern: bytes) -> int:
         """``FmIndex::count`` (with_slice.rs:5-8)."""
@@ -571,39 +615,50 @@ class FmIndex:
                            cap=(1 << 16) if cap is None else cap)[2:]
 
     # -- longest-suffix match (greedy backward seeding) ---------------------
-    def match(self, pattern: bytes) -> Tuple[int, int, int]:
+    def match(self, pattern: bytes, strands: str = "forward"):
         """(length, lo, hi): the longest suffix of `pattern` that occurs in the
         text and its suffix-array interval (hi - lo occurrences; (0, 0, 0)
-        when not even the last symbol occurs)."""
-        lens, rng = self.match_batch([pattern], locate=False)
-        return int(lens[0]), int(rng[0, 0]), int(rng[0, 1])
+        when not even the last symbol occurs).  strands="reverse": of the
+        pattern's reverse complement; "both": a (forward, reverse) pair."""
+        lens, rng = self.match_batch([pattern], locate=False, strands=strands)
+        res = [(int(lens[v]), int(rng[v, 0]), int(rng[v, 1])) for v in range(lens.size)]
+        return tuple(res) if strands == "both" else res[0]
 
     def match_batch(self, patterns, reversed: bool = False, locate: bool = True, min_len: int = 1,
-                    max_occ: Optional[int] = None):
+                    max_occ: Optional[int] = None, strands: str = "forward"):
         """Longest-suffix match of many patterns (fmx_match_batch): (lens
         uint32[n], ranges P[n, 2]) and, with `locate`, (..., loc_offsets
         uint64[n+1], locations P[total]).  lens[i] is the length of the longest
         suffix of pattern i that occurs in the text and ranges[i] = (lo, hi) its
         interval, always the true values; locations (suffix-array-row order)
         are emitted only for patterns with lens[i] >= max(min_len, 1) and
-        hi - lo <= max_occ (None: no bound)."""
+        hi - lo <= max_occ (None: no bound).  `strands` (here and in
+        seeds_batch / approx_batch; needs set_complement): "reverse" answers
+        for each pattern's reverse complement rc(p)[j] = map[p[m-1-j]] instead,
+        "both" for the 2n patterns p_0, rc(p_0), p_1, rc(p_1), ... — every
+        array then has 2n patterns' entries, flat, and positions within a
+        reverse strand are in rc(p)'s own coordinates."""
         outs = lambda n: (np.zeros(max(n, 1), dtype=np.uint32), np.zeros((max(n, 1), 2), dtype=self._dt))  # noqa: E731
         n, (lens, rng), loff, locs = _host_query("fmx_match_batch", self._h, self._dt, patterns, reversed,
-                                                 (int(min_len),), max_occ, outs, locate=locate)
+                                                 (int(min_len),), max_occ, outs, locate=locate, strands=strands)
         return (lens[:n], rng[:n]) + ((loff, locs) if locate else ())
 
     # -- greedy seed chains (the match restarted until the pattern is used up) --
     def seeds(self, pattern: bytes, max_seeds: int = 8, min_len: int = 1, skip: int = 0,
-              max_occ: Optional[int] = None) -> List[Tuple[int, int, int, int]]:
+              max_occ: Optional[int] = None, strands: str = "forward"):
         """The pattern's seeds, right to left: [(end, len, lo, hi)], seed j
         covering pattern[end - len:end] with suffix-array interval [lo, hi).
-        (max_occ only selects which seeds seeds_batch locates.)"""
-        ns, _, spans, rng = self.seeds_batch([pattern], max_seeds, min_len, skip, max_occ, locate=False)
-        return [(int(spans[0, j, 0]), int(spans[0, j, 1]), int(rng[0, j, 0]), int(rng[0, j, 1]))
-                for j in range(int(ns[0]))]
+        (max_occ only selects which seeds seeds_batch locates.)  strands=
+        "both": a (forward, reverse) pair of such lists."""
+        ns, _, spans, rng = self.seeds_batch([pattern], max_seeds, min_len, skip, max_occ, locate=False,
+                                             strands=strands)
+        res = [[(int(spans[v, j, 0]), int(spans[v, j, 1]), int(rng[v, j, 0]), int(rng[v, j, 1]))
+                for j in range(int(ns[v]))] for v in range(ns.size)]
+        return tuple(res) if strands == "both" else res[0]
 
     def seeds_batch(self, patterns, max_seeds: int = 8, min_len: int = 1, skip: int = 0,
-                    max_occ: Optional[int] = None, reversed: bool = False, locate: bool = True):
+                    max_occ: Optional[int] = None, reversed: bool = False, locate: bool = True,
+                    strands: str = "forward"):
         """Greedy seed chains of many patterns (fmx_seeds_batch): (nseeds
         uint32[n], rest uint32[n], spans uint32[n, max_seeds, 2], ranges P[n,
         max_seeds, 2]) and, with `locate`, (..., loc_offsets uint64[n *
@@ -622,23 +677,27 @@ class FmIndex:
                     np.zeros((rows, 2), dtype=np.uint32), np.zeros((rows, 2), dtype=self._dt))
 
         n, (ns, rest, spans, rng), loff, locs = _host_query("fmx_seeds_batch", self._h, self._dt, patterns, reversed,
-                                                            (ms, int(min_len), int(skip)), max_occ, outs, ms, locate)
+                                                            (ms, int(min_len), int(skip)), max_occ, outs, ms, locate,
+                                                            strands=strands)
         return ((ns[:n], rest[:n], spans[:n * ms].reshape(n, ms, 2), rng[:n * ms].reshape(n, ms, 2))
                 + ((loff, locs) if locate else ()))
 
     # -- k-mismatch search (substitutions only, a bounded backtracking walk on the device) --
-    def approx(self, pattern: bytes, max_mm: int = 1, max_hits: int = 8,
-               best: bool = False) -> List[Tuple[int, List[Tuple[int, int]], int, int]]:
+    def approx(self, pattern: bytes, max_mm: int = 1, max_hits: int = 8, best: bool = False,
+               strands: str = "forward"):
         """The pattern's variants within max_mm substitutions that occur in
         the text, in the contract's order: [(d, [(pos, sym), ...], lo, hi)],
         the d substitutions by decreasing position (sym a symbol index), [lo,
-        hi) the variant's suffix-array interval; at most max_hits of them."""
-        nh, _, mm, subs, rng = self.approx_batch([pattern], max_mm, max_hits, best, locate=False)
-        return [(int(mm[0, j]), [(int(subs[0, j, t, 0]), int(subs[0, j, t, 1])) for t in range(int(mm[0, j]))],
-                 int(rng[0, j, 0]), int(rng[0, j, 1])) for j in range(int(nh[0]))]
+        hi) the variant's suffix-array interval; at most max_hits of them.
+        strands="both": a (forward, reverse) pair of such lists."""
+        nh, _, mm, subs, rng = self.approx_batch([pattern], max_mm, max_hits, best, locate=False, strands=strands)
+        res = [[(int(mm[v, j]), [(int(subs[v, j, t, 0]), int(subs[v, j, t, 1])) for t in range(int(mm[v, j]))],
+                 int(rng[v, j, 0]), int(rng[v, j, 1])) for j in range(int(nh[v]))] for v in range(nh.size)]
+        return tuple(res) if strands == "both" else res[0]
 
     def approx_batch(self, patterns, max_mm: int = 1, max_hits: int = 8, best: bool = False,
-                     max_occ: Optional[int] = None, reversed: bool = False, locate: bool = True):
+                     max_occ: Optional[int] = None, reversed: bool = False, locate: bool = True,
+                     strands: str = "forward"):
         """k-mismatch search of many patterns (fmx_approx_batch): (nhits
         uint32[n], more uint32[n], mm uint32[n, max_hits], subs uint32[n,
         max_hits, 3, 2], ranges P[n, max_hits, 2]) and, with `locate`, (...,
@@ -663,7 +722,8 @@ class FmIndex:
 
         params = (int(max_mm), mh, _n.FMX_APPROX_BEST if best else 0)
         n, (nh, more, mm, subs, rng), loff, locs = _host_query("fmx_approx_batch", self._h, self._dt, patterns,
-                                                               reversed, params, max_occ, outs, mh, locate)
+                                                               reversed, params, max_occ, outs, mh, locate,
+                                                               strands=strands)
         return ((nh[:n], more[:n], mm[:n * mh].reshape(n, mh), subs[:n * mh].reshape(n, mh, 3, 2),
                  rng[:n * mh].reshape(n, mh, 2)) + ((loff, locs) if locate else ()))
 
@@ -697,13 +757,15 @@ class FmIndex:
                           d_loc_offsets: int = 0, d_locs: int = 0, cap: int = 0, d_needed: int = 0, d_ws: int = 0,
                           ws_bytes: int = 0, min_len: int = 1, max_occ: Optional[int] = None, stream: int = 0,
                           reversed: bool = False, long_patterns: bool = False, stage_kb: int = 0,
-                          fixed_len: int = 0) -> None:
-        """fmx_match_batch_async: d_lens uint32[n], d_ranges P[2 n]; with
+                          fixed_len: int = 0, strands: str = "forward") -> None:
+        """(strands="both", here and in the next two: n reads, every size below
+        with 2 n for n.)
+        fmx_match_batch_async: d_lens uint32[n], d_ranges P[2 n]; with
         d_loc_offsets (uint64[n+1]) also the locations of the reporting
         patterns, into d_locs (cap entries) with the total in d_needed, over a
         workspace of locate_workspace_size(n) bytes; d_loc_offsets = 0:
         lengths and intervals only, no workspace."""
-        flags = _flags(reversed, long_patterns, stage_kb, fixed_len)
+        flags = _flags(reversed, long_patterns, stage_kb, fixed_len) | _strand_flags(strands)
         _check(_n.lib().fmx_match_batch_async(
             self._h, C.c_void_p(d_bytes), C.c_void_p(d_offsets), n, flags, int(min_len),
             (1 << 64) - 1 if max_occ is None else int(max_occ), C.c_void_p(d_lens), C.c_void_p(d_ranges),
@@ -713,14 +775,15 @@ class FmIndex:
                           d_ranges: int, d_loc_offsets: int = 0, d_locs: int = 0, cap: int = 0, d_needed: int = 0,
                           d_ws: int = 0, ws_bytes: int = 0, max_seeds: int = 8, min_len: int = 1, skip: int = 0,
                           max_occ: Optional[int] = None, stream: int = 0, reversed: bool = False,
-                          long_patterns: bool = False, stage_kb: int = 0, fixed_len: int = 0) -> None:
+                          long_patterns: bool = False, stage_kb: int = 0, fixed_len: int = 0,
+                          strands: str = "forward") -> None:
         """fmx_seeds_batch_async: d_nseeds, d_rest uint32[n], d_spans uint32[2 n
         max_seeds], d_ranges P[2 n max_seeds]; with d_loc_offsets (uint64[n
         max_seeds + 1]) also the locations of the reporting seeds, into d_locs
         (cap entries) with the total in d_needed, over a workspace of
         locate_workspace_size(n * max_seeds) bytes; d_loc_offsets = 0: spans
         and intervals only, no workspace."""
-        flags = _flags(reversed, long_patterns, stage_kb, fixed_len)
+        flags = _flags(reversed, long_patterns, stage_kb, fixed_len) | _strand_flags(strands)
         _check(_n.lib().fmx_seeds_batch_async(
             self._h, C.c_void_p(d_bytes), C.c_void_p(d_offsets), n, flags, int(max_seeds), int(min_len), int(skip),
             (1 << 64) - 1 if max_occ is None else int(max_occ), _vp(d_nseeds), _vp(d_rest), _vp(d_spans), _vp(d_ranges),
@@ -730,14 +793,15 @@ class FmIndex:
                            d_subs: int, d_ranges: int, d_loc_offsets: int = 0, d_locs: int = 0, cap: int = 0,
                            d_needed: int = 0, d_ws: int = 0, ws_bytes: int = 0, max_mm: int = 1, max_hits: int = 8,
                            best: bool = False, max_occ: Optional[int] = None, stream: int = 0, reversed: bool = False,
-                           long_patterns: bool = False, stage_kb: int = 0, fixed_len: int = 0) -> None:
+                           long_patterns: bool = False, stage_kb: int = 0, fixed_len: int = 0,
+                           strands: str = "forward") -> None:
         """fmx_approx_batch_async: d_nhits, d_more uint32[n], d_mm uint32[n
         max_hits], d_subs uint32[6 n max_hits], d_ranges P[2 n max_hits]; with
         d_loc_offsets (uint64[n max_hits + 1]) also the locations of the
         reporting hits, into d_locs (cap entries) with the total in d_needed,
         over a workspace of locate_workspace_size(n * max_hits) bytes;
         d_loc_offsets = 0: intervals only, no workspace."""
-        flags = _flags(reversed, long_patterns, stage_kb, fixed_len)
+        flags = _flags(reversed, long_patterns, stage_kb, fixed_len) | _strand_flags(strands)
         _check(_n.lib().fmx_approx_batch_async(
             self._h, C.c_void_p(d_bytes), C.c_void_p(d_offsets), n, flags, int(max_mm), int(max_hits),
             _n.FMX_APPROX_BEST if best else 0, (1 << 64) - 1 if max_occ is None else int(max_occ), _vp(d_nhits),

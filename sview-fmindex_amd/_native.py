@@ -28,6 +28,8 @@ FMX_ENC_TABLE = 0
 FMX_ENC_PASS = 1
 FMX_PATTERN_REVERSED = 1
 FMX_HINT_LONG_PATTERNS = 2
+FMX_PATTERN_REVCOMP = 4
+FMX_BOTH_STRANDS = 8
 FMX_APPROX_BEST = 1
 FMX_OCC_BLOB = 0
 FMX_OCC_INTERLEAVED = 1
@@ -88,6 +90,8 @@ SIGNATURES = {
     "fmx_free": (None, [_p]),
     "fmx_blob": (_p, [_p, _PU64]),
     "fmx_info": (_i, [_p, C.POINTER(fmx_index_info)]),
+    "fmx_set_complement": (_i, [_p, C.c_char_p]),
+    "fmx_get_complement": (_i, [_p, C.c_char_p]),
     "fmx_count_batch": (_i, [_p, _p, _p, _u64, _u32, _p]),
     "fmx_locate_batch": (_i, [_p, _p, _p, _u64, _u32, _p, _p, _u64, _PU64]),
     "fmx_count_batch_async": (_i, [_p, _p, _p, _u64, _u32, _p, _p]),

@@ -1157,11 +1157,50 @@ fmx_status fmx_info(const fmx_index *ix, fmx_index_info *o) {
     return FMX_OK;
 }
 
+// The strand flags' complement map: the index keeps the map itself and, in HBM
+// (QueryTables::enc_rc), the table the strand kernels read bytes through.
+fmx_status fmx_set_complement(fmx_index *ix, const uint8_t *map) {
+    if (!ix) return FMX_E_ARG;
+    std::lock_guard<std::mutex> g(ix->mu);
+    if (!map) {
+        ix->has_comp = false;
+        return FMX_OK;
+    }
+    DeviceGuard dg(ix->device);
+    uint8_t enc_rc[256];
+    for (int b = 0; b < 256; ++b) enc_rc[b] = ix->qa.enc[map[b]];
+    if (ix->stage.h2d(ix->d_tab->enc_rc, enc_rc, 256, ix->stream) != hipSuccess ||
+        hipStreamSynchronize(ix->stream) != hipSuccess)
+        return FMX_E_DEVICE;
+    memcpy(ix->comp, map, 256);
+    ix->has_comp = true;
+    return FMX_OK;
+}
+
+fmx_status fmx_get_complement(const fmx_index *ix, uint8_t *map_out) {
+    if (!ix || !map_out) return FMX_E_ARG;
+    std::lock_guard<std::mutex> g(const_cast<fmx_index *>(ix)->mu);
+    if (!ix->has_comp) return FMX_E_ARG;
+    memcpy(map_out, ix->comp, 256);
+    return FMX_OK;
+}
+
+// A slot query's strand flags: at most one of them, and only with a map.
+static bool strand_flags_ok(const fmx_index *ix, uint32_t flags) {
+    return !(flags & kStrandFlags) || ((flags & kStrandFlags) != kStrandFlags && ix->has_comp);
+}
+// Its virtual pattern count (two per read under FMX_BOTH_STRANDS), or false when that overflows.
+static bool virtual_patterns(uint64_t n, uint32_t flags, uint64_t *nv) {
+    if ((flags & FMX_BOTH_STRANDS) && n > ~0ull / 2) return false;
+    *nv = (flags & FMX_BOTH_STRANDS) ? 2 * n : n;
+    return true;
+}
+
 // ---------------------------------------------------------------- async
 
 fmx_status fmx_count_batch_async(fmx_index *ix, const uint8_t *d_bytes, const uint64_t *d_offsets, uint64_t n,
                                  uint32_t flags, void *d_counts, void *stream) {
-    if (!ix || (n && (!d_bytes || !d_offsets || !d_counts))) return FMX_E_ARG;
+    if (!ix || (flags & kStrandFlags) || (n && (!d_bytes || !d_offsets || !d_counts))) return FMX_E_ARG;
     hipStream_t s = stream ? (hipStream_t)stream : ix->stream;
     DeviceGuard dg(ix->device);
     return with_status(ix, s, [&](uint32_t *status) {
@@ -1206,7 +1245,7 @@ fmx_status fmx_locate_batch_async(fmx_index *ix, const uint8_t *d_bytes, const u
                                   uint32_t flags, void *d_counts, uint64_t *d_loc_offsets, void *d_locs,
                                   uint64_t cap, uint64_t *d_needed, void *d_ws, uint64_t ws_bytes, void *stream) {
     if (!ix || !d_loc_offsets || !d_needed || (n && (!d_bytes || !d_offsets)) || (cap && !d_locs)) return FMX_E_ARG;
-    if (!ws_ok(d_ws, ws_bytes)) return FMX_E_ARG;
+    if ((flags & kStrandFlags) || !ws_ok(d_ws, ws_bytes)) return FMX_E_ARG;
     hipStream_t s = stream ? (hipStream_t)stream : ix->stream;
     DeviceGuard dg(ix->device);
     if (n == 0) return dev_err(zero_locs(d_loc_offsets, d_needed, s));
@@ -1259,6 +1298,7 @@ fmx_status fmx_match_batch_async(fmx_index *ix, const uint8_t *d_bytes, const ui
                                  uint64_t *d_loc_offsets, void *d_locs, uint64_t cap, uint64_t *d_needed, void *d_ws,
                                  uint64_t ws_bytes, void *stream) {
     if (!ix || (n && (!d_bytes || !d_offsets || !d_lens || !d_ranges))) return FMX_E_ARG;
+    if (!strand_flags_ok(ix, flags) || !virtual_patterns(n, flags, &n)) return FMX_E_ARG;  // (n: virtual from here)
     return slot_query(ix, "match", n, n, d_loc_offsets, d_locs, cap, d_needed, d_ws, ws_bytes, stream,
                       [&](const LocOut &out, uint32_t *status, hipStream_t s) {
                           return launch_match(ix, d_bytes, d_offsets, n, flags, min_len, max_occ, d_lens, d_ranges, out,
@@ -1271,7 +1311,8 @@ fmx_status fmx_seeds_batch_async(fmx_index *ix, const uint8_t *d_bytes, const ui
                                  uint32_t *d_nseeds, uint32_t *d_rest, uint32_t *d_spans, void *d_ranges,
                                  uint64_t *d_loc_offsets, void *d_locs, uint64_t cap, uint64_t *d_needed, void *d_ws,
                                  uint64_t ws_bytes, void *stream) {
-    if (!ix || !slots_shape_ok(n, max_seeds, kMaxSeeds)) return FMX_E_ARG;
+    if (!ix || !strand_flags_ok(ix, flags) || !virtual_patterns(n, flags, &n)) return FMX_E_ARG;  // (n: virtual)
+    if (!slots_shape_ok(n, max_seeds, kMaxSeeds)) return FMX_E_ARG;
     if (n && (!d_bytes || !d_offsets || !d_nseeds || !d_rest || !d_spans || !d_ranges)) return FMX_E_ARG;
     return slot_query(ix, "seeds", n, n * max_seeds, d_loc_offsets, d_locs, cap, d_needed, d_ws, ws_bytes, stream,
                       [&](const LocOut &out, uint32_t *status, hipStream_t s) {
@@ -1290,7 +1331,8 @@ fmx_status fmx_approx_batch_async(fmx_index *ix, const uint8_t *d_bytes, const u
                                   uint32_t *d_nhits, uint32_t *d_more, uint32_t *d_mm, uint32_t *d_subs,
                                   void *d_ranges, uint64_t *d_loc_offsets, void *d_locs, uint64_t cap,
                                   uint64_t *d_needed, void *d_ws, uint64_t ws_bytes, void *stream) {
-    if (!ix || !approx_shape_ok(n, max_mm, max_hits, mode)) return FMX_E_ARG;
+    if (!ix || !strand_flags_ok(ix, flags) || !virtual_patterns(n, flags, &n)) return FMX_E_ARG;  // (n: virtual)
+    if (!approx_shape_ok(n, max_mm, max_hits, mode)) return FMX_E_ARG;
     if (n && (!d_bytes || !d_offsets || !d_nhits || !d_more || !d_mm || !d_subs || !d_ranges)) return FMX_E_ARG;
     return slot_query(ix, "approx", n, n * max_hits, d_loc_offsets, d_locs, cap, d_needed, d_ws, ws_bytes, stream,
                       [&](const LocOut &out, uint32_t *status, hipStream_t s) {
@@ -1318,7 +1360,7 @@ fmx_status fmx_locate_group_async(fmx_index *ix, const fmx_locate_job *jobs, uin
         const fmx_locate_job &j = jobs[i];
         if (!j.d_loc_offsets || !j.d_needed || (j.n_patterns && (!j.d_bytes || !j.d_offsets)) ||
             (j.cap && !j.d_locs) || !j.d_workspace || j.workspace_bytes < ws_bytes_for(ix, j.n_patterns) ||
-            ((uintptr_t)j.d_workspace & 15) != 0 || j.reserved != 0)
+            ((uintptr_t)j.d_workspace & 15) != 0 || j.reserved != 0 || (j.flags & kStrandFlags))
             return FMX_E_ARG;
         for (uint64_t k = 0; k < i; ++k)
             if (jobs[k].d_workspace == j.d_workspace) return FMX_E_ARG;  // the batches run concurrently
@@ -1415,9 +1457,12 @@ static fmx_status check_patterns(const uint64_t *offsets, uint64_t n) {
 // = the most bytes any 256-pattern tile spans, rounded up to whole KB (tiles
 // past 56 KB read their patterns from HBM), and FMX_HINT_FIXED_LEN when every
 // pattern has the same length.
-static uint32_t stage_hint(const uint64_t *offsets, uint64_t n) {
+// Under FMX_BOTH_STRANDS a tile is 128 reads and holds both strands' copies.
+static uint32_t stage_hint(const uint64_t *offsets, uint64_t n, uint32_t flags = 0) {
+    const uint64_t tile = (flags & FMX_BOTH_STRANDS) ? 128 : 256, copies = (flags & FMX_BOTH_STRANDS) ? 2 : 1;
     uint64_t most = 0;
-    for (uint64_t t = 0; t < n; t += 256) most = std::max(most, offsets[std::min(n, t + 256)] - offsets[t]);
+    for (uint64_t t = 0; t < n; t += tile)
+        most = std::max(most, copies * (offsets[std::min(n, t + tile)] - offsets[t]));
     const uint64_t kb = std::min<uint64_t>(std::max<uint64_t>((most + 1023) / 1024, 1), kStageBytesLong / 1024);
     const uint64_t m = offsets[1] - offsets[0];
     bool fixed = m <= 0xffffu;
@@ -1427,7 +1472,7 @@ static uint32_t stage_hint(const uint64_t *offsets, uint64_t n) {
 
 fmx_status fmx_count_batch(fmx_index *ix, const uint8_t *bytes, const uint64_t *offsets, uint64_t n,
                            uint32_t flags, void *out_counts) {
-    if (!ix || (n && (!offsets || !out_counts))) return FMX_E_ARG;
+    if (!ix || (flags & kStrandFlags) || (n && (!offsets || !out_counts))) return FMX_E_ARG;
     if (n == 0) return FMX_OK;
     std::lock_guard<std::mutex> g(ix->mu);
     fmx_status st = check_patterns(offsets, n);
@@ -1488,7 +1533,8 @@ struct Carve {
     Out outs[8];
     uint32_t n_outs = 0;
     uint32_t flags;  // the caller's direction with the batch's own hints (stage_hint)
-    Carve(const uint64_t *offsets, uint64_t n, uint32_t flags_) : flags((flags_ & 0xffu) | stage_hint(offsets, n)) {
+    Carve(const uint64_t *offsets, uint64_t n, uint32_t flags_)
+        : flags((flags_ & 0xffu) | stage_hint(offsets, n, flags_)) {
         add(std::max<uint64_t>(offsets[n], 1));
         o_off = add((n + 1) * 8);
     }
@@ -1565,7 +1611,7 @@ static fmx_status host_query(fmx_index *ix, Carve &c, const uint8_t *bytes, cons
 fmx_status fmx_locate_batch(fmx_index *ix, const uint8_t *bytes, const uint64_t *offsets, uint64_t n,
                             uint32_t flags, uint64_t *out_loc_offsets, void *out_locs, uint64_t cap,
                             uint64_t *needed) {
-    if (!ix || !out_loc_offsets || (n && !offsets) || (cap && !out_locs)) return FMX_E_ARG;
+    if (!ix || (flags & kStrandFlags) || !out_loc_offsets || (n && !offsets) || (cap && !out_locs)) return FMX_E_ARG;
     if (needed) *needed = 0;
     if (n == 0) { out_loc_offsets[0] = 0; return FMX_OK; }
     const fmx_status st = check_patterns(offsets, n);
@@ -1588,6 +1634,8 @@ fmx_status fmx_match_batch(fmx_index *ix, const uint8_t *bytes, const uint64_t *
                            uint64_t *out_loc_offsets, void *out_locs, uint64_t cap, uint64_t *needed) {
     const bool loc = out_loc_offsets != nullptr;
     if (!ix || (n && (!offsets || !out_lens || !out_ranges)) || (loc && cap && !out_locs)) return FMX_E_ARG;
+    uint64_t nv;  // the virtual patterns: the outputs' shape
+    if (!strand_flags_ok(ix, flags) || !virtual_patterns(n, flags, &nv)) return FMX_E_ARG;
     if (needed) *needed = 0;
     if (n == 0) {
         if (loc) out_loc_offsets[0] = 0;
@@ -1595,8 +1643,8 @@ fmx_status fmx_match_batch(fmx_index *ix, const uint8_t *bytes, const uint64_t *
     }
     if (!offsets_ok(bytes, offsets, n)) return FMX_E_ARG;
     Carve c(offsets, n, flags);
-    const uint64_t o_len = c.add(n * 4, out_lens), o_rng = c.add(2 * n * ix->bv.L.pos_bytes, out_ranges);
-    return host_query(ix, c, bytes, offsets, n, n, true, out_loc_offsets, out_locs, cap, needed,
+    const uint64_t o_len = c.add(nv * 4, out_lens), o_rng = c.add(2 * nv * ix->bv.L.pos_bytes, out_ranges);
+    return host_query(ix, c, bytes, offsets, n, nv, true, out_loc_offsets, out_locs, cap, needed,
                       [&](uint8_t *d, uint64_t dcap, hipStream_t s) {
                           return fmx_match_batch_async(ix, d, (uint64_t *)(d + c.o_off), n, c.flags, min_len, max_occ,
                                                        (uint32_t *)(d + o_len), d + o_rng,
@@ -1612,7 +1660,9 @@ fmx_status fmx_seeds_batch(fmx_index *ix, const uint8_t *bytes, const uint64_t *
                            uint32_t *out_rest, uint32_t *out_spans, void *out_ranges, uint64_t *out_loc_offsets,
                            void *out_locs, uint64_t cap, uint64_t *needed) {
     const bool loc = out_loc_offsets != nullptr;
-    if (!ix || !slots_shape_ok(n, max_seeds, kMaxSeeds)) return FMX_E_ARG;
+    uint64_t nv;  // the virtual patterns: the outputs' shape
+    if (!ix || !strand_flags_ok(ix, flags) || !virtual_patterns(n, flags, &nv)) return FMX_E_ARG;
+    if (!slots_shape_ok(nv, max_seeds, kMaxSeeds)) return FMX_E_ARG;
     if ((n && (!offsets || !out_nseeds || !out_rest || !out_spans || !out_ranges)) || (loc && cap && !out_locs))
         return FMX_E_ARG;
     if (needed) *needed = 0;
@@ -1621,9 +1671,9 @@ fmx_status fmx_seeds_batch(fmx_index *ix, const uint8_t *bytes, const uint64_t *
         return FMX_OK;
     }
     if (!offsets_ok(bytes, offsets, n)) return FMX_E_ARG;
-    const uint64_t pb = ix->bv.L.pos_bytes, slots = n * max_seeds;
+    const uint64_t pb = ix->bv.L.pos_bytes, slots = nv * max_seeds;
     Carve c(offsets, n, flags);
-    const uint64_t o_ns = c.add(n * 4, out_nseeds), o_rest = c.add(n * 4, out_rest);
+    const uint64_t o_ns = c.add(nv * 4, out_nseeds), o_rest = c.add(nv * 4, out_rest);
     const uint64_t o_span = c.add(2 * slots * 4, out_spans), o_rng = c.add(2 * slots * pb, out_ranges);
     return host_query(ix, c, bytes, offsets, n, slots, false, out_loc_offsets, out_locs, cap, needed,
                       [&](uint8_t *d, uint64_t dcap, hipStream_t s) {
@@ -1641,7 +1691,9 @@ fmx_status fmx_approx_batch(fmx_index *ix, const uint8_t *bytes, const uint64_t 
                             uint32_t *out_more, uint32_t *out_mm, uint32_t *out_subs, void *out_ranges,
                             uint64_t *out_loc_offsets, void *out_locs, uint64_t cap, uint64_t *needed) {
     const bool loc = out_loc_offsets != nullptr;
-    if (!ix || !approx_shape_ok(n, max_mm, max_hits, mode)) return FMX_E_ARG;
+    uint64_t nv;  // the virtual patterns: the outputs' shape
+    if (!ix || !strand_flags_ok(ix, flags) || !virtual_patterns(n, flags, &nv)) return FMX_E_ARG;
+    if (!approx_shape_ok(nv, max_mm, max_hits, mode)) return FMX_E_ARG;
     if ((n && (!offsets || !out_nhits || !out_more || !out_mm || !out_subs || !out_ranges)) ||
         (loc && cap && !out_locs))
         return FMX_E_ARG;
@@ -1651,9 +1703,9 @@ fmx_status fmx_approx_batch(fmx_index *ix, const uint8_t *bytes, const uint64_t 
         return FMX_OK;
     }
     if (!offsets_ok(bytes, offsets, n)) return FMX_E_ARG;
-    const uint64_t pb = ix->bv.L.pos_bytes, slots = n * max_hits;
+    const uint64_t pb = ix->bv.L.pos_bytes, slots = nv * max_hits;
     Carve c(offsets, n, flags);
-    const uint64_t o_nh = c.add(n * 4, out_nhits), o_more = c.add(n * 4, out_more), o_mm = c.add(slots * 4, out_mm);
+    const uint64_t o_nh = c.add(nv * 4, out_nhits), o_more = c.add(nv * 4, out_more), o_mm = c.add(slots * 4, out_mm);
     const uint64_t o_subs = c.add(6 * slots * 4, out_subs), o_rng = c.add(2 * slots * pb, out_ranges);
     return host_query(ix, c, bytes, offsets, n, slots, false, out_loc_offsets, out_locs, cap, needed,
                       [&](uint8_t *d, uint64_t dcap, hipStream_t s) {

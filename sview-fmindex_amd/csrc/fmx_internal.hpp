@@ -69,6 +69,7 @@ struct QueryTables {
     uint8_t dig[kMaxSigma];  // = QueryArgs::dlut_dig
     uint64_t C[kMaxSigma + 1];
     uint64_t mult[kMaxK];
+    uint8_t enc_rc[256];  // enc o complement (fmx_set_complement; read by the strand kernels only)
 };
 
 // Kernel arguments for the query kernels (passed by value; < 2 KB).  Arrays
@@ -259,6 +260,9 @@ struct fmx_index {
     uint64_t safull_bytes = 0;
     uint8_t *d_text = nullptr;
     fmx::QueryTables *d_tab = nullptr;
+    // the complement map of the strand flags (fmx_set_complement; under `mu`), d_tab->enc_rc derived from it
+    uint8_t comp[256] = {};
+    std::atomic<bool> has_comp{false};
     uint32_t options = 0;
     fmx::QueryArgs qa{};
     // host-API scratch (grown on demand) and its private locate workspace
@@ -371,7 +375,17 @@ struct LocOut {
 // FMX_PATTERN_REVERSED and FMX_HINT_FIXED_LEN of a call's flags, as the batch structs hold them
 inline uint32_t flags_rev(uint32_t flags) { return (flags & FMX_PATTERN_REVERSED) ? 1u : 0u; }
 inline uint32_t flags_stride(uint32_t flags) { return flags >> 16; }
-// k_match: every pattern's matched length and interval.
+// The strand instantiation of a slot-query kernel (fmx_kernels.hpp, strand_pattern): none, every pattern as its
+// reverse complement (FMX_PATTERN_REVCOMP), or both strands interleaved (FMX_BOTH_STRANDS).  The launchers and
+// the batch structs then count VIRTUAL patterns (2 per read under kStrandBoth); bytes, offsets and the stride
+// stay the reads'.
+constexpr int kStrandNone = 0, kStrandRc = 1, kStrandBoth = 2;
+constexpr uint32_t kStrandFlags = FMX_PATTERN_REVCOMP | FMX_BOTH_STRANDS;
+inline int flags_strand(uint32_t flags) {
+    return (flags & FMX_BOTH_STRANDS) ? kStrandBoth : (flags & FMX_PATTERN_REVCOMP) ? kStrandRc : kStrandNone;
+}
+// k_match: every pattern's matched length and interval.  (The launchers below take n = the VIRTUAL pattern
+// count of a strand launch, flags_strand(flags); the outputs are shaped by it.)
 struct MatchBatch {
     const uint8_t *bytes;
     const uint64_t *offs;
@@ -561,14 +575,15 @@ struct LayoutOps {
     hipError_t (*emit_chain)(const QueryArgs &qa, uint32_t vb, uint32_t rec, const LocateGroup &grp, uint32_t tiles,
                              uint64_t tag, uint64_t late_ticks, hipStream_t s);
     // longest-suffix match (k_match): every record encoding, no search variant
-    hipError_t (*match)(const QueryArgs &qa, uint32_t vb, uint32_t rec, const MatchBatch &mb, uint32_t tiles,
-                        uint32_t sb, hipStream_t s);
+    // (strand: kStrandNone / kStrandRc / kStrandBoth picks the instantiation, here and in the next two)
+    hipError_t (*match)(const QueryArgs &qa, uint32_t vb, uint32_t rec, int strand, const MatchBatch &mb,
+                        uint32_t tiles, uint32_t sb, hipStream_t s);
     // greedy seed chains (k_seeds): as match
-    hipError_t (*seeds)(const QueryArgs &qa, uint32_t vb, uint32_t rec, const SeedBatch &sb, uint32_t wgs,
+    hipError_t (*seeds)(const QueryArgs &qa, uint32_t vb, uint32_t rec, int strand, const SeedBatch &sb, uint32_t wgs,
                         uint32_t stage, hipStream_t s);
     // k-mismatch search (k_approx): as match
-    hipError_t (*approx)(const QueryArgs &qa, uint32_t vb, uint32_t rec, const ApproxBatch &ab, uint32_t wgs,
-                         uint32_t stage, hipStream_t s);
+    hipError_t (*approx)(const QueryArgs &qa, uint32_t vb, uint32_t rec, int strand, const ApproxBatch &ab,
+                         uint32_t wgs, uint32_t stage, hipStream_t s);
 };
 uint64_t locate_tiles_cap(uint64_t n);
 // Bytes per pattern of the search-result records in the locate workspace.

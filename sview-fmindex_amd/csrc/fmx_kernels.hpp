@@ -416,6 +416,98 @@ __device__ __forceinline__ PatView lane_pattern(const Tables<P> &s, uint8_t *s_p
     return pattern_view(s, s_pat, staged, bytes, beg, end, b0, b1, rev);
 }
 
+// The strand instantiations (ST = kStrandRc: FMX_PATTERN_REVCOMP, kStrandBoth:
+// FMX_BOTH_STRANDS; fmx.h).  The kernel's npat counts VIRTUAL patterns, and
+// lane t of workgroup b owns virtual pattern v = 256 b + t: under kStrandRc
+// rc(read v), under kStrandBoth strand v & 1 of read v >> 1 — a tile is 128
+// reads.  rc(p) is p's bytes read in the opposite direction through enc_rc =
+// enc o complement, so the other strand is a second view of the same bytes:
+// the staging loop loads each 16-B vector of the tile's reads once and writes
+// strand 0 through enc in pattern order at s_pat[0, span) (kStrandBoth only)
+// and strand 1 through enc_rc in the opposite order behind it (the mirror
+// image of the forward writes: the same bytes per bank per instruction, so no
+// bank conflict the forward copy does not have); both copies must fit
+// stage_bytes.  A tile that does not fit is read raw: strand 1's view has rev
+// toggled and enc = s_rc.  s_rc: the strand kernels' own 256-B LDS copy of
+// QueryTables::enc_rc.  Offsets and FMX_HINT_FIXED_LEN are those of the reads,
+// checked as stage_patterns checks them.  Ends with the barrier lane_pattern
+// ends with; has / staged as there (a lane without a pattern: m = 0).
+template <int ST, typename P>
+__device__ __forceinline__ PatView strand_pattern(const QueryArgs &a, const Tables<P> &s, uint8_t *s_rc, uint8_t *s_pat,
+                                                  const uint8_t *__restrict__ bytes, const uint64_t *offs,
+                                                  uint64_t npat, uint64_t first, bool rev, uint32_t stage_bytes,
+                                                  uint32_t stride, uint32_t *status, bool &has, bool &staged) {
+    constexpr bool both = ST == kStrandBoth;
+    s_rc[threadIdx.x] = a.tab->enc_rc[threadIdx.x];
+    const uint64_t nreads = both ? npat >> 1 : npat, per_tile = both ? 128u : 256u;
+    const uint64_t r0 = both ? first >> 1 : first, r1 = r0 + per_tile < nreads ? r0 + per_tile : nreads;
+    const uint64_t v = first + threadIdx.x, i = both ? v >> 1 : v;
+    const bool rc = !both || (v & 1) != 0;  // this lane's strand
+    has = v < npat;
+    uint64_t b0, b1, beg, end, chk;
+    if (stride) {
+        b0 = r0 * stride;
+        b1 = r1 * stride;
+        beg = has ? i * stride : 0;
+        end = has ? beg + stride : 0;
+        chk = has ? offs[i + 1] : 0;
+        if (first == 0 && threadIdx.x == 0 && offs[0] != 0) atomicOr(status, kStatusStride);
+    } else {
+        b0 = offs[r0];
+        b1 = offs[r1];
+        beg = has ? offs[i] : 0;
+        end = has ? offs[i + 1] : 0;
+        chk = end;
+    }
+    if (chk != end) atomicOr(status, kStatusStride);
+    const uint64_t len = b1 - b0;
+    // the tables (stage_tables and s_rc, written by every thread) are read below
+    __syncthreads();
+    staged = len <= stage_bytes / (both ? 2u : 1u);
+    if (staged) {
+        using V4 = uint32_t __attribute__((ext_vector_type(4)));
+        // (stage_patterns' loop: vectors aligned by address, only those holding a byte of the span)
+        const uint64_t addr = reinterpret_cast<uint64_t>(bytes) + b0, a0 = addr & ~15ull;
+        const uint32_t lead = (uint32_t)(addr - a0), len32 = (uint32_t)len;
+        const uint32_t nv = len32 ? (lead + len32 + 15) >> 4 : 0u;
+        const V4 *src = reinterpret_cast<const V4 *>(a0);
+        uint8_t *s_fw = s_pat, *s_bw = s_pat + (both ? len32 : 0u);
+        for (uint32_t v0 = 0; v0 < nv; v0 += 4 * 256) {
+            V4 x[4];
+#pragma unroll
+            for (uint32_t u = 0; u < 4; ++u) {
+                const uint32_t q = v0 + u * 256 + threadIdx.x;
+                if (q < nv) x[u] = src[q];
+            }
+#pragma unroll
+            for (uint32_t u = 0; u < 4; ++u) {
+                const uint32_t q = v0 + u * 256 + threadIdx.x;
+                if (q >= nv) continue;
+                const uint32_t base = 16u * q - lead;
+#pragma unroll
+                for (uint32_t w = 0; w < 16; ++w) {
+                    const uint32_t x0 = base + w;
+                    if (x0 >= len32) continue;
+                    const uint32_t c = (x[u][w >> 2] >> (8 * (w & 3))) & 0xffu;
+                    const uint32_t at = rev ? len32 - 1u - x0 : x0;  // the span in pattern order
+                    if (both) s_fw[at] = s.enc[c];
+                    s_bw[len32 - 1u - at] = s_rc[c];
+                }
+            }
+        }
+    }
+    __syncthreads();
+    PatView pv;
+    pv.m = end - beg;
+    pv.raw = bytes + beg;
+    pv.rev = rev != rc;
+    pv.enc = rc ? s_rc : s.enc;
+    // strand 0 as pattern_view; strand 1's span is mirrored, so the read's copy starts where its end was
+    const uint64_t fw = rev ? b1 - end : beg - b0, bw = rev ? beg - b0 : b1 - end;
+    pv.sym = !staged ? nullptr : rc ? s_pat + (both ? len : 0) + bw : s_pat + fw;
+    return pv;
+}
+
 // The workgroup's records: after the workspace's 2 G tile words, from the workgroup's first slot.
 template <typename P>
 __device__ __forceinline__ SearchRec<P> *slot_records(uint64_t *tiles, uint64_t G, uint64_t slot0) {
@@ -467,7 +559,7 @@ __device__ __forceinline__ void store_tile_counts(uint64_t *tiles, const unsigne
 // text and its interval (match_suffix), always written.  The slot reports when
 // the length is at least max(min_len, 1) too; its one row is located as
 // search_lane does (locate_one).
-template <typename P, int N, int VB, int REC>
+template <typename P, int N, int VB, int REC, int ST = kStrandNone>
 __global__ __launch_bounds__(256, 8) void k_match(const QueryArgs a, const MatchBatch B, uint32_t stage_bytes) {
     __shared__ Tables<P> s;
     FMX_DYN_LDS(s_pat);  // stage_bytes, then the k-mer table (dynamic)
@@ -480,14 +572,25 @@ __global__ __launch_bounds__(256, 8) void k_match(const QueryArgs a, const Match
     const uint64_t npat = B.npat, first = (uint64_t)blockIdx.x * 256u;
     const bool rev = B.rev != 0;
     uint64_t beg, end, b0, b1;
-    const bool staged =
-        stage_patterns(s, s_pat, bytes, B.offs, npat, first, rev, stage_bytes, B.stride, a.status, beg, end, b0, b1);
-    __syncthreads();
+    bool staged;
+    PatView spv;  // (a strand instantiation's view: strand_pattern)
+    if constexpr (ST != kStrandNone) {
+        __shared__ uint8_t s_rc[256];
+        bool has;
+        spv = strand_pattern<ST>(a, s, s_rc, s_pat, bytes, B.offs, npat, first, rev, stage_bytes, B.stride, a.status,
+                                 has, staged);
+    } else {
+        staged = stage_patterns(s, s_pat, bytes, B.offs, npat, first, rev, stage_bytes, B.stride, a.status, beg, end,
+                                b0, b1);
+        __syncthreads();
+    }
     const uint64_t i = first + threadIdx.x;
     const bool loc = B.tiles != nullptr;  // (workgroup-uniform)
     uint64_t cnt = 0;
     if (i < npat) {
-        const PatView pv = pattern_view(s, s_pat, staged, bytes, beg, end, b0, b1, rev);
+        PatView pv;
+        if constexpr (ST != kStrandNone) pv = spv;
+        else pv = pattern_view(s, s_pat, staged, bytes, beg, end, b0, b1, rev);
         P lo, hi;
         uint32_t len;
         SampledRow<P> smp;
@@ -518,7 +621,7 @@ __global__ __launch_bounds__(256, 8) void k_match(const QueryArgs a, const Match
 // at least max(min_len, 1) symbols is a seed): per slot the seed's (end,
 // length) and (lo, hi).  One row with a sampled row seen in that restart's own
 // single-row phase (SampledRow) is located here by that one read.
-template <typename P, int N, int VB, int REC>
+template <typename P, int N, int VB, int REC, int ST = kStrandNone>
 __global__ __launch_bounds__(256, 8) void k_seeds(const QueryArgs a, const SeedBatch B, uint32_t stage_bytes) {
     __shared__ Tables<P> s;
     FMX_DYN_LDS(s_pat);  // stage_bytes, then the k-mer table (dynamic)
@@ -528,8 +631,14 @@ __global__ __launch_bounds__(256, 8) void k_seeds(const QueryArgs a, const SeedB
     const uint64_t npat = B.npat, first = (uint64_t)blockIdx.x * 256u;
     const bool rev = B.rev != 0;
     bool has, staged;
-    PatView pv =
-        lane_pattern(s, s_pat, B.bytes, B.offs, npat, first, rev, stage_bytes, B.stride, a.status, has, staged);
+    PatView pv;
+    if constexpr (ST != kStrandNone) {
+        __shared__ uint8_t s_rc[256];
+        pv = strand_pattern<ST>(a, s, s_rc, s_pat, B.bytes, B.offs, npat, first, rev, stage_bytes, B.stride, a.status,
+                                has, staged);
+    } else {
+        pv = lane_pattern(s, s_pat, B.bytes, B.offs, npat, first, rev, stage_bytes, B.stride, a.status, has, staged);
+    }
     const uint32_t ms = B.max_seeds;
     const bool loc = B.tiles != nullptr;  // (workgroup-uniform)
     const uint64_t G = (npat * ms + 255) / 256;  // the batch's 256-slot tiles
@@ -544,7 +653,8 @@ __global__ __launch_bounds__(256, 8) void k_seeds(const QueryArgs a, const SeedB
         uint32_t ls = threadIdx.x * ms;  // seed j's slot in the workgroup
         const uint32_t ls_end = ls + ms;
         const uint32_t need = B.min_len > 1u ? B.min_len : 1u;
-        const bool raw_rev = rev && !staged;
+        // (a strand instantiation's raw views differ in direction lane by lane)
+        const bool raw_rev = (ST != kStrandNone ? pv.rev : rev) && !staged;
         while (pv.m > 0 && ls < ls_end) {
             P lo, hi;
             uint32_t len;
@@ -586,7 +696,7 @@ __global__ __launch_bounds__(256, 8) void k_seeds(const QueryArgs a, const SeedB
 // substitutions (3 pairs of position, symbol, the unused pairs zero) and (lo,
 // hi) per slot — and ends the search at the (max_hits + 1)-th (more = 1).  No
 // sampled row is tracked across the backtracking.
-template <typename P, int N, int VB, int REC>
+template <typename P, int N, int VB, int REC, int ST = kStrandNone>
 __global__ __launch_bounds__(256, 5) void k_approx(const QueryArgs a, const ApproxBatch B, uint32_t stage_bytes) {
     __shared__ Tables<P> s;
     FMX_DYN_LDS(s_pat);  // stage_bytes, then the k-mer table (dynamic)
@@ -595,8 +705,15 @@ __global__ __launch_bounds__(256, 5) void k_approx(const QueryArgs a, const Appr
     if (threadIdx.x < kMaxHits) s_tile[threadIdx.x] = 0;  // (visible after lane_pattern's barrier)
     const uint64_t npat = B.npat, first = (uint64_t)blockIdx.x * 256u;
     bool has, staged;
-    const PatView pv = lane_pattern(s, s_pat, B.bytes, B.offs, npat, first, B.rev != 0, stage_bytes, B.stride, a.status,
-                                    has, staged);
+    PatView pv;
+    if constexpr (ST != kStrandNone) {
+        __shared__ uint8_t s_rc[256];
+        pv = strand_pattern<ST>(a, s, s_rc, s_pat, B.bytes, B.offs, npat, first, B.rev != 0, stage_bytes, B.stride,
+                                a.status, has, staged);
+    } else {
+        pv = lane_pattern(s, s_pat, B.bytes, B.offs, npat, first, B.rev != 0, stage_bytes, B.stride, a.status, has,
+                          staged);
+    }
     const uint32_t mh = B.max_hits;
     const bool loc = B.tiles != nullptr;         // (workgroup-uniform)
     const uint64_t G = (npat * mh + 255) / 256;  // the batch's 256-slot tiles

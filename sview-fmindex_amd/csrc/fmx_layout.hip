@@ -179,26 +179,38 @@ hipError_t disp(uint32_t vb, uint32_t rec, F &&f) {
     });
 }
 
-[[maybe_unused]] hipError_t op_match(const QueryArgs &qa, uint32_t vb, uint32_t rec, const MatchBatch &mb, uint32_t tiles,
-                                     uint32_t sb, hipStream_t s) {
+// The slot queries: the instantiation without strands, or one of the two strand instantiations (kStrandRc,
+// kStrandBoth), by `strand`.
+#define FMX_LAUNCH_STRAND(kernel, strand, grid, lds, ...)                                                          \
+    do {                                                                                                            \
+        if ((strand) == kStrandNone)                                                                                \
+            hipLaunchKernelGGL((kernel<P, N, VB, R>), dim3(grid), dim3(256), lds, s, __VA_ARGS__);                  \
+        else if ((strand) == kStrandRc)                                                                             \
+            hipLaunchKernelGGL((kernel<P, N, VB, R, kStrandRc>), dim3(grid), dim3(256), lds, s, __VA_ARGS__);       \
+        else                                                                                                        \
+            hipLaunchKernelGGL((kernel<P, N, VB, R, kStrandBoth>), dim3(grid), dim3(256), lds, s, __VA_ARGS__);     \
+    } while (0)
+
+[[maybe_unused]] hipError_t op_match(const QueryArgs &qa, uint32_t vb, uint32_t rec, int strand, const MatchBatch &mb,
+                                     uint32_t tiles, uint32_t sb, hipStream_t s) {
     return disp(vb, rec, [&]<int VB, int R>() {
-        hipLaunchKernelGGL((k_match<P, N, VB, R>), dim3(tiles), dim3(256), sb + qa.kt_lds_bytes, s, qa, mb, sb);
+        FMX_LAUNCH_STRAND(k_match, strand, tiles, sb + qa.kt_lds_bytes, qa, mb, sb);
         return hipGetLastError();
     });
 }
 
-[[maybe_unused]] hipError_t op_seeds(const QueryArgs &qa, uint32_t vb, uint32_t rec, const SeedBatch &sb, uint32_t wgs,
-                                     uint32_t stage, hipStream_t s) {
+[[maybe_unused]] hipError_t op_seeds(const QueryArgs &qa, uint32_t vb, uint32_t rec, int strand, const SeedBatch &sb,
+                                     uint32_t wgs, uint32_t stage, hipStream_t s) {
     return disp(vb, rec, [&]<int VB, int R>() {
-        hipLaunchKernelGGL((k_seeds<P, N, VB, R>), dim3(wgs), dim3(256), stage + qa.kt_lds_bytes, s, qa, sb, stage);
+        FMX_LAUNCH_STRAND(k_seeds, strand, wgs, stage + qa.kt_lds_bytes, qa, sb, stage);
         return hipGetLastError();
     });
 }
 
-[[maybe_unused]] hipError_t op_approx(const QueryArgs &qa, uint32_t vb, uint32_t rec, const ApproxBatch &ab, uint32_t wgs,
-                                      uint32_t stage, hipStream_t s) {
+[[maybe_unused]] hipError_t op_approx(const QueryArgs &qa, uint32_t vb, uint32_t rec, int strand, const ApproxBatch &ab,
+                                      uint32_t wgs, uint32_t stage, hipStream_t s) {
     return disp(vb, rec, [&]<int VB, int R>() {
-        hipLaunchKernelGGL((k_approx<P, N, VB, R>), dim3(wgs), dim3(256), stage + qa.kt_lds_bytes, s, qa, ab, stage);
+        FMX_LAUNCH_STRAND(k_approx, strand, wgs, stage + qa.kt_lds_bytes, qa, ab, stage);
         return hipGetLastError();
     });
 }

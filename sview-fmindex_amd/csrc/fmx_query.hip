@@ -691,7 +691,19 @@ hipError_t launch_locate(const fmx_index *ix, const uint8_t *d_bytes, const uint
 
 // The slot queries (fmx_internal.hpp, LocOut): the query's own kernel, then —
 // when locations are asked for — the locate's last kernels over the records it
-// left, one "pattern" per slot.
+// left, one "pattern" per slot.  n counts the virtual patterns of a strand
+// launch (flags_strand(flags): the kernel's strand instantiation).
+
+// A slot query's stage.  A strand launch with FMX_HINT_FIXED_LEN asks for no more dynamic LDS than its tile
+// spans (256 m bytes: 256 reads' one copy, or 128 reads' two): the strand kernels hold 256 B more static LDS
+// (enc_rc), which costs a workgroup per CU where the KB-rounded hint sits at an occupancy edge (150 bp reads,
+// a 38 KB stage: 4 x 40,976 B is 64 B past a CU's 160 KB, profiles/r12/README.md).  Launches without a strand
+// flag: stage_bytes_for, as ever.
+static uint32_t slot_stage_bytes(uint32_t flags) {
+    const uint32_t sb = stage_bytes_for(flags), m = flags_stride(flags);
+    if (flags_strand(flags) == kStrandNone || m == 0) return sb;
+    return std::min<uint32_t>(sb, (256u * m + 15u) & ~15u);
+}
 
 // Whether a launch takes `slots` slots: their 256-slot tiles, and with locations the workspace's room for them
 static bool slots_ok(uint64_t slots, const LocOut &out) {
@@ -723,7 +735,8 @@ hipError_t launch_match(const fmx_index *ix, const uint8_t *d_bytes, const uint6
     const MatchBatch mb{d_bytes, d_offsets, n, d_lens, d_ranges, loc ? out.tiles : nullptr, max_occ, min_len,
                         flags_rev(flags), flags_stride(flags)};
     const Disp d = dispatch(ix);
-    const hipError_t e = d.ops->match(qa, d.vb, d.rec, mb, (uint32_t)((n + 255) / 256), stage_bytes_for(flags), stream);
+    const hipError_t e = d.ops->match(qa, d.vb, d.rec, flags_strand(flags), mb, (uint32_t)((n + 255) / 256),
+                                      slot_stage_bytes(flags), stream);
     return e != hipSuccess || !loc ? e : emit_slots(ix, qa, n, out, stream);
 }
 
@@ -743,7 +756,8 @@ hipError_t launch_seeds(const fmx_index *ix, const uint8_t *d_bytes, const uint6
                        d_ranges, loc ? out.tiles : nullptr,    max_occ, max_seeds, min_len, skip,
                        flags_rev(flags), flags_stride(flags)};
     const Disp d = dispatch(ix);
-    const hipError_t e = d.ops->seeds(qa, d.vb, d.rec, sb, (uint32_t)wgs, stage_bytes_for(flags), stream);
+    const hipError_t e =
+        d.ops->seeds(qa, d.vb, d.rec, flags_strand(flags), sb, (uint32_t)wgs, slot_stage_bytes(flags), stream);
     return e != hipSuccess || !loc ? e : emit_slots(ix, qa, slots, out, stream);
 }
 
@@ -764,7 +778,8 @@ hipError_t launch_approx(const fmx_index *ix, const uint8_t *d_bytes, const uint
                          d_subs,  d_ranges,  loc ? out.tiles : nullptr,  max_occ, max_mm, max_hits,
                          (mode & FMX_APPROX_BEST) ? 1u : 0u, flags_rev(flags), flags_stride(flags)};
     const Disp d = dispatch(ix);
-    const hipError_t e = d.ops->approx(qa, d.vb, d.rec, ab, (uint32_t)wgs, stage_bytes_for(flags), stream);
+    const hipError_t e =
+        d.ops->approx(qa, d.vb, d.rec, flags_strand(flags), ab, (uint32_t)wgs, slot_stage_bytes(flags), stream);
     return e != hipSuccess || !loc ? e : emit_slots(ix, qa, slots, out, stream);
 }
 
