@@ -10,11 +10,15 @@ max_hits) bytes — 16 B past a 256-B boundary, the pattern bytes at the given
 skew, flush against the end guard).  After the launch: every guard byte
 intact, the inputs unchanged, every output the expected value,
 d_locs[min(cap, total):cap] still the prefill.  Batches of 257 and 700
-patterns run once more with a 1 KB stage: the unstaged path of k_approx."""
+patterns run once more with a 1 KB stage: the unstaged path of k_approx.
+run_approx also takes an explicit pattern list with its own parameters and
+hints (tests/_long_cases.py: reads of mapper length, which tile is staged and
+which is raw asserted from the offsets)."""
 import numpy as np
 
 from _approx_cases import batch, expected_arrays
 from _guard_cases import FILL_OUT, Arena
+from _strand_cases import staged_tiles
 
 MAX_MM, MAX_HITS, MAX_OCC = 2, 3, 3
 BATCH_SIZES = (1, 257, 700)
@@ -24,14 +28,22 @@ CAPS = ("total", "total-1", "zero-null")
 LAYOUTS = [(4, 3, 64), (8, 5, 128)]
 
 
-def run_approx(pkg, ix, mem_cls, case, orc, pb, n, cap_name, skew, reversed, locate=True, stage_kb=0, best=False):
+def run_approx(pkg, ix, mem_cls, case, orc, pb, n, cap_name, skew, reversed, locate=True, stage_kb=0, best=False,
+               pats=None, params=None, fixed_len=0, long_patterns=False, tiles=None):
     """stage_kb: FMX_HINT_STAGE_KB; 1 leaves no full tile of these batches room
-    in LDS, so k_approx reads every pattern from HBM."""
-    pats = batch(case, n, MAX_MM)
-    mh = MAX_HITS
-    exp = expected_arrays(case, orc, pats, MAX_MM, mh, best, MAX_OCC)
+    in LDS, so k_approx reads every pattern from HBM.
+    pats: the patterns (n of them) in place of batch(case, n), whose class
+    check is then the caller's; params: (max_mm, max_hits, max_occ) in place of
+    the module's; fixed_len, long_patterns: the other hints; tiles: the
+    caller's list of staged (True) and raw tiles, asserted against
+    _strand_cases.staged_tiles() in place of the stage_kb check below."""
+    own = pats is None
+    max_mm, mh, max_occ = params or (MAX_MM, MAX_HITS, MAX_OCC)
+    pats = batch(case, n, max_mm) if own else pats
+    assert len(pats) == n
+    exp = expected_arrays(case, orc, pats, max_mm, mh, best, max_occ)
     total = int(exp[5][-1])
-    if n >= 256:
+    if own and n >= 256:
         cnt = np.diff(exp[5].astype(np.int64))
         stored = exp[4][:, :, 1].reshape(-1) > 0
         assert total > n // 2 and (cnt[stored] == 0).sum() >= 4 and (~stored).sum() >= 100, "every slot reports"
@@ -39,7 +51,10 @@ def run_approx(pkg, ix, mem_cls, case, orc, pb, n, cap_name, skew, reversed, loc
     if cap < 0:
         return  # (a batch with no location has no cap below its total)
     what = f"approx n={n} cap={cap_name}({cap}) skew={skew} rev={reversed} locate={locate} stage_kb={stage_kb}"
-    if stage_kb:
+    if tiles is not None:
+        got = staged_tiles(pats, "forward", stage_kb, fixed_len, long_patterns)
+        assert got == list(tiles), f"tiles staged by their offsets: {got}, expected {list(tiles)}"
+    elif stage_kb:
         tile_bytes = [sum(len(p) for p in pats[t:t + 256]) for t in range(0, n, 256)]
         # (every full tile; the one-pattern last tile of a 257-pattern batch still fits)
         assert min(tile_bytes[:n // 256]) > 1024 * stage_kb, "a full tile fits the stage: not the unstaged path"
@@ -71,7 +86,8 @@ def run_approx(pkg, ix, mem_cls, case, orc, pb, n, cap_name, skew, reversed, loc
     p = arena.ptr
     assert p("bytes") % 16 == skew and p("ranges") % 16 == pb % 16
     assert all(p(x) % 16 == 4 for x in ("nhits", "more", "mm", "subs"))
-    kw = dict(max_mm=MAX_MM, max_hits=mh, best=best, max_occ=MAX_OCC, reversed=reversed, stage_kb=stage_kb)
+    kw = dict(max_mm=max_mm, max_hits=mh, best=best, max_occ=max_occ, reversed=reversed, stage_kb=stage_kb,
+              fixed_len=fixed_len, long_patterns=long_patterns)
     outs = (p("nhits"), p("more"), p("mm"), p("subs"), p("ranges"))
     if locate:
         assert p("ws") % 256 == 16

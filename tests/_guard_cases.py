@@ -22,6 +22,9 @@ No correct or incorrect kernel of this engine strays further than a 16-B
 vector, and d_locs is followed by guard bytes for every location past cap (an
 emit that ignored cap would write them all), so nothing leaves the
 allocation: a regression is a failed assert.
+run_match also takes an explicit pattern list with its own parameters and
+hints (tests/_long_cases.py: reads of mapper length, which tile is staged and
+which is raw asserted from the offsets).
 """
 import ctypes as C
 
@@ -516,17 +519,34 @@ def match_batch(case, orc, n):
     return pats
 
 
-def run_match(pkg, ix, mem_cls, case, orc, pb, n, cap_name, skew, reversed, locate=True):
+def run_match(pkg, ix, mem_cls, case, orc, pb, n, cap_name, skew, reversed, locate=True, pats=None, params=None,
+              stage_kb=None, fixed_len=0, long_patterns=False, tiles=None):
     """fmx_match_batch_async, with locations (min_len / max_occ keep the
     shortest and the heaviest matches from reporting) or lengths and intervals
-    only (no location buffers, no workspace)."""
-    pats = match_batch(case, orc, n)
+    only (no location buffers, no workspace).
+    pats: the patterns (n of them) in place of match_batch(case, orc, n),
+    whose class check is then the caller's; params: (min_len, max_occ) in place
+    of the module's; stage_kb: FMX_HINT_STAGE_KB (None: what stages every tile;
+    0: no hint), fixed_len, long_patterns: the other hints; tiles: the caller's
+    list of staged (True) and raw tiles, asserted against
+    _strand_cases.staged_tiles()."""
+    own = pats is None
+    pats = match_batch(case, orc, n) if own else pats
+    assert len(pats) == n
+    min_len, max_occ = params or (MATCH_MIN_LEN, MATCH_MAX_OCC)
+    if stage_kb is None:
+        stage_kb = stage_kb_of(pats)
+    if tiles is not None:
+        from _strand_cases import staged_tiles  # (it imports this module)
+        got = staged_tiles(pats, "forward", stage_kb, fixed_len, long_patterns)
+        assert got == list(tiles), f"tiles staged by their offsets: {got}, expected {list(tiles)}"
+    hints = dict(stage_kb=stage_kb, fixed_len=fixed_len, long_patterns=long_patterns)
     exp = [case.expected(orc, p) for p in pats]
-    rep = [e[0] >= MATCH_MIN_LEN and e[2] - e[1] <= MATCH_MAX_OCC for e in exp]
+    rep = [e[0] >= min_len and e[2] - e[1] <= max_occ for e in exp]
     cnt = np.array([e[2] - e[1] if r else 0 for e, r in zip(exp, rep)], np.uint64)
     off = np.concatenate([np.zeros(1, np.uint64), np.cumsum(cnt, dtype=np.uint64)])
     locs = np.array([x for e, r in zip(exp, rep) if r for x in e[3]], np.uint64)
-    if n >= 255:
+    if own and n >= 255:
         assert sum(rep) >= 64 and sum(not r and e[0] > 0 for e, r in zip(exp, rep)) >= 4, "every pattern reports"
     cap = 0
     if locate:
@@ -543,11 +563,11 @@ def run_match(pkg, ix, mem_cls, case, orc, pb, n, cap_name, skew, reversed, loca
     assert b.p("lens") % 16 == 4 and b.p("ranges") % 16 == pb % 16
     if locate:
         ix.match_batch_async(b.p("bytes"), b.p("offsets"), n, b.p("lens"), b.p("ranges"), b.p("loc_offsets"),
-                             b.p("locs"), cap, b.p("needed"), b.p("ws"), b.ws_bytes, min_len=MATCH_MIN_LEN,
-                             max_occ=MATCH_MAX_OCC, reversed=reversed, stage_kb=stage_kb_of(pats))
+                             b.p("locs"), cap, b.p("needed"), b.p("ws"), b.ws_bytes, min_len=min_len,
+                             max_occ=max_occ, reversed=reversed, **hints)
     else:
-        ix.match_batch_async(b.p("bytes"), b.p("offsets"), n, b.p("lens"), b.p("ranges"), min_len=MATCH_MIN_LEN,
-                             max_occ=MATCH_MAX_OCC, reversed=reversed, stage_kb=stage_kb_of(pats))
+        ix.match_batch_async(b.p("bytes"), b.p("offsets"), n, b.p("lens"), b.p("ranges"), min_len=min_len,
+                             max_occ=max_occ, reversed=reversed, **hints)
     ix.sync()
     arena.image()
     arena.check_guards_and_inputs(what)

@@ -26,14 +26,19 @@ BATCH_SIZES = (1, 255, 256, 257, 700)
 
 class Case:
     """One text: `nchars` distinct printable bytes plus a wildcard symbol that
-    does not occur in it (symbol_count = nchars + 1), k and sr in 1..4."""
+    does not occur in it (symbol_count = nchars + 1), k and sr in 1..4.
+    n_text: a text of exactly that many symbols from a stream of its own (the
+    alphabet, k and sr stay what they are without it) in place of the 300 to
+    4,000 of the default."""
 
-    def __init__(self, seed, nchars, k=None, sr=None):
+    def __init__(self, seed, nchars, k=None, sr=None, n_text=None):
         rng = np.random.default_rng(seed)
         self.chars = rand_chr_list(rng, nchars)
         self.table = table_from_symbols([bytes([c]) for c in self.chars], with_wildcard=True)
         self.sigma = nchars + 1
         self.text = rand_text(rng, self.chars, 300, 4000)
+        if n_text is not None:
+            self.text = rand_text(np.random.default_rng(seed + 7), self.chars, n_text, n_text)
         self.k = int(rng.integers(1, 5)) if k is None else k
         self.sr = int(rng.integers(1, 5)) if sr is None else sr
         while (self.sigma + 1) ** self.k > 1 << 20:

@@ -10,11 +10,15 @@ max_seeds) bytes — 16 B past a 256-B boundary, the pattern bytes at the given
 skew, flush against the end guard).  After the launch: every guard byte
 intact, the inputs unchanged, every output the expected value,
 d_locs[min(cap, total):cap] still the prefill.  Batches of 257 and 700
-patterns run once more with a 1 KB stage: the unstaged path of k_seeds."""
+patterns run once more with a 1 KB stage: the unstaged path of k_seeds.
+run_seeds also takes an explicit pattern list with its own parameters and
+hints (tests/_long_cases.py: reads of mapper length, which tile is staged and
+which is raw asserted from the offsets)."""
 import numpy as np
 
 from _guard_cases import FILL_OUT, Arena
 from _seed_cases import batch, expected_arrays
+from _strand_cases import staged_tiles
 
 MAX_SEEDS, MIN_LEN, SKIP, MAX_OCC = 3, 2, 1, 3
 BATCH_SIZES = (1, 257, 700)
@@ -24,15 +28,23 @@ CAPS = ("total", "total-1", "zero-null")
 LAYOUTS = [(4, 3, 64), (8, 5, 128)]
 
 
-def run_seeds(pkg, ix, mem_cls, case, orc, pb, n, cap_name, skew, reversed, locate=True, stage_kb=0):
+def run_seeds(pkg, ix, mem_cls, case, orc, pb, n, cap_name, skew, reversed, locate=True, stage_kb=0, pats=None,
+              params=None, fixed_len=0, long_patterns=False, tiles=None):
     """stage_kb: FMX_HINT_STAGE_KB; 1 leaves no tile of these batches room in
     LDS, so k_seeds reads every pattern from HBM (the unstaged prefix view: a
-    reversed pattern's raw pointer advanced with each restart)."""
-    pats = batch(case, n)
-    ms = MAX_SEEDS
-    exp = expected_arrays(case, orc, pats, ms, MIN_LEN, SKIP, MAX_OCC)
+    reversed pattern's raw pointer advanced with each restart).
+    pats: the patterns (n of them) in place of batch(case, n), whose class
+    check is then the caller's; params: (max_seeds, min_len, skip, max_occ) in
+    place of the module's; fixed_len, long_patterns: the other hints; tiles:
+    the caller's list of staged (True) and raw tiles, asserted against
+    _strand_cases.staged_tiles() in place of the stage_kb check below."""
+    own = pats is None
+    pats = batch(case, n) if own else pats
+    assert len(pats) == n
+    ms, min_len, skip, max_occ = params or (MAX_SEEDS, MIN_LEN, SKIP, MAX_OCC)
+    exp = expected_arrays(case, orc, pats, ms, min_len, skip, max_occ)
     total = int(exp[4][-1])
-    if n >= 256:
+    if own and n >= 256:
         cnt = np.diff(exp[4].astype(np.int64))
         stored = exp[2][:, :, 1].reshape(-1) > 0
         assert total > n and (cnt[stored] == 0).sum() >= 4 and (~stored).sum() >= 100, "every slot reports"
@@ -40,7 +52,10 @@ def run_seeds(pkg, ix, mem_cls, case, orc, pb, n, cap_name, skew, reversed, loca
     if cap < 0:
         return  # (a batch with no location has no cap below its total)
     what = f"seeds n={n} cap={cap_name}({cap}) skew={skew} rev={reversed} locate={locate} stage_kb={stage_kb}"
-    if stage_kb:
+    if tiles is not None:
+        got = staged_tiles(pats, "forward", stage_kb, fixed_len, long_patterns)
+        assert got == list(tiles), f"tiles staged by their offsets: {got}, expected {list(tiles)}"
+    elif stage_kb:
         tile_bytes = [sum(len(p) for p in pats[t:t + 256]) for t in range(0, n, 256)]
         # (every full tile; the one-pattern last tile of a 257-pattern batch still fits)
         assert min(tile_bytes[:n // 256]) > 1024 * stage_kb, "a full tile fits the stage: not the unstaged path"
@@ -70,7 +85,8 @@ def run_seeds(pkg, ix, mem_cls, case, orc, pb, n, cap_name, skew, reversed, loca
     assert off + nb == arena.size - 4096, "the last pattern byte is not the byte before the end guard"
     p = arena.ptr
     assert p("bytes") % 16 == skew and p("spans") % 16 == 4 and p("nseeds") % 16 == 4 and p("ranges") % 16 == pb % 16
-    kw = dict(max_seeds=ms, min_len=MIN_LEN, skip=SKIP, max_occ=MAX_OCC, reversed=reversed, stage_kb=stage_kb)
+    kw = dict(max_seeds=ms, min_len=min_len, skip=skip, max_occ=max_occ, reversed=reversed, stage_kb=stage_kb,
+              fixed_len=fixed_len, long_patterns=long_patterns)
     if locate:
         assert p("ws") % 256 == 16
         ix.seeds_batch_async(p("bytes"), p("offsets"), n, p("nseeds"), p("rest"), p("spans"), p("ranges"),

@@ -1,7 +1,9 @@
 """The `simt` fixture of the SIMT test modules: tests/simt/libfmx_simt.so (the
 engine's own sources compiled for the CPU against the SIMT shim) built, bound
 with the package's SIGNATURES and swapped in for the engine library while the
-module's tests run.  A module binds it with `simt = simt_fixture(...)`."""
+module's tests run.  A module binds it with `simt = simt_fixture(...)`.
+simt_lds_log / simt_lds_log_get: the shim's log of each launch's dynamic LDS
+request and of the bytes of it every workgroup wrote (test_long_simt.py)."""
 import ctypes as C
 import os
 import subprocess
@@ -20,6 +22,8 @@ SHIM = {
     "simt_defer": (None, [C.c_int, C.c_double]),
     "simt_selftest_defer": (C.c_int, []),
     "simt_block_order": (None, [C.c_int]),
+    "simt_lds_log": (None, [C.c_int]),
+    "simt_lds_log_get": (C.c_uint64, [C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.c_uint64]),
 }
 
 

@@ -21,6 +21,10 @@ Reads: text substrings alternating with reads whose rc is a text substring (so
 strand 1 truly matches), then the substituted and absent-byte classes of
 _match_cases.Case.core().  assert_classes checks on the reference alone that
 both strands hold whole matches and partial ones.
+
+stage_bytes_of / staged_tiles restate, from the offsets alone, which tiles a
+launch stages under its hints; run_device and the flag-less runners assert a
+caller's expectation of that (tiles=) for the reads of tests/_long_cases.py.
 """
 import numpy as np
 
@@ -217,8 +221,27 @@ def stage_kb_both(reads, strands):
     return min(max(-(-most // 1024), 1), 56)
 
 
+def stage_bytes_of(strands="forward", stage_kb=0, fixed_len=0, long_patterns=False):
+    """The stage of a slot-query launch by the rules of include/fmx.h: the
+    FMX_HINT_STAGE_KB hint (at most 56 KB), else 56 KB with
+    FMX_HINT_LONG_PATTERNS, else 16 KB; a strand launch with FMX_HINT_FIXED_LEN
+    asks for no more than its tile spans (256 m bytes, rounded up to 16)."""
+    sb = min(stage_kb, 56) * 1024 if stage_kb else 56 * 1024 if long_patterns else 16 * 1024
+    if strands != "forward" and fixed_len:
+        sb = min(sb, -(-256 * fixed_len // 16) * 16)
+    return sb
+
+
+def staged_tiles(reads, strands="forward", stage_kb=0, fixed_len=0, long_patterns=False):
+    """Per tile (256 reads, 128 under "both"), from the offsets alone: whether
+    its span (both copies under "both") fits the launch's stage."""
+    tile, copies = (128, 2) if strands == "both" else (256, 1)
+    sb = stage_bytes_of(strands, stage_kb, fixed_len, long_patterns)
+    return [copies * sum(len(p) for p in reads[t:t + tile]) <= sb for t in range(0, len(reads), tile)]
+
+
 def run_device(pkg, ix, mem_cls, case, orc, pb, query, reads, cmap, strands, reversed=False, locate=True,
-               cap_name="total", skew=1, stage_kb=None, fixed_len=0, **over):
+               cap_name="total", skew=1, stage_kb=None, fixed_len=0, long_patterns=False, tiles=None, **over):
     """The _async call with every buffer carved at its exact (2n-shaped) size
     and weakest alignment out of one guard-filled allocation (_guard_cases.
     Arena): the pattern bytes at `skew`, flush against the end guard, 4-B
@@ -226,7 +249,10 @@ def run_device(pkg, ix, mem_cls, case, orc, pb, query, reads, cmap, strands, rev
     past a 256-B boundary.  After the launch: every guard byte intact, the
     inputs unchanged, every output the expected value, *d_needed exact and
     d_locs[min(cap, total):cap] still the prefill.  stage_kb: None = the hint
-    that stages every tile; 1 = no full tile fits (the raw path)."""
+    that stages every tile; 1 = no full tile fits (the raw path).  tiles: the
+    caller's list of which tiles are staged (True) and which raw, asserted
+    against staged_tiles() in place of that check of an explicit stage_kb (0 =
+    no hint); long_patterns: FMX_HINT_LONG_PATTERNS."""
     kw = kw_for(query, **over)
     n = len(reads)
     vpats = expand(reads, cmap, strands)
@@ -237,9 +263,13 @@ def run_device(pkg, ix, mem_cls, case, orc, pb, query, reads, cmap, strands, rev
     cap = {"total": total, "total-1": total - 1, "zero-null": 0}[cap_name] if locate else 0
     if cap < 0:
         return
-    if stage_kb is None:
+    hinted = stage_kb is not None
+    if not hinted:
         stage_kb = stage_kb_both(reads, strands)
-    elif n >= (128 if strands == "both" else 256):
+    if tiles is not None:
+        got = staged_tiles(reads, strands, stage_kb, fixed_len, long_patterns)
+        assert got == list(tiles), f"tiles staged by their offsets: {got}, expected {list(tiles)}"
+    elif hinted and n >= (128 if strands == "both" else 256):
         tile, copies = (128, 2) if strands == "both" else (256, 1)
         assert copies * sum(len(p) for p in reads[:tile]) > 1024 * stage_kb, "the first tile fits: not the raw path"
     what = (f"{query} strands={strands} n={n} cap={cap_name}({cap}) skew={skew} rev={reversed} locate={locate} "
@@ -269,7 +299,7 @@ def run_device(pkg, ix, mem_cls, case, orc, pb, query, reads, cmap, strands, rev
     if locate:
         args += [p("loc_offsets"), p("locs"), cap, p("needed"), p("ws"), wsb]
     getattr(ix, query + "_batch_async")(*args, reversed=reversed, stage_kb=stage_kb, fixed_len=fixed_len,
-                                        strands=strands, **kw)
+                                        long_patterns=long_patterns, strands=strands, **kw)
     ix.sync()
     arena.image()
     arena.check_guards_and_inputs(what)

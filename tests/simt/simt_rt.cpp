@@ -149,6 +149,15 @@ bool g_bar_site_set = false;
 std::string g_fail;
 hipError_t g_last = hipSuccess;
 uint64_t g_grids = 0, g_items = 0, g_switches = 0;
+// simt_lds_log: per grid that asked for dynamic LDS, the request and, per workgroup (by index), how many
+// bytes of it the workgroup left different from the random fill it started with
+struct LdsLog {
+    uint64_t dyn_bytes;
+    std::vector<uint32_t> changed;
+};
+bool g_lds_log_on = false;
+std::vector<LdsLog> g_lds_log;
+std::vector<uint8_t> g_dyn_before;
 
 // A fault inside a kernel (an out-of-bounds access the GPU might not have
 // caught) prints the work-item, the workgroup and a backtrace (resolve the
@@ -327,12 +336,15 @@ hipError_t run_grid(dim3 grid, dim3 block, size_t dyn_bytes, const std::function
     if (!g_ordered) std::shuffle(order.begin(), order.end(), g_rng);
     const uint32_t nwaves = (uint32_t)((nt + 63) / 64);
     g_fail.clear();
+    const bool log_lds = g_lds_log_on && dyn_bytes > 0;
+    if (log_lds) g_lds_log.push_back(LdsLog{dyn_bytes, std::vector<uint32_t>(nb, 0u)});
     for (uint64_t bi : order) {
         g_bid = dim3((uint32_t)(bi % grid.x), (uint32_t)((bi / grid.x) % grid.y), (uint32_t)(bi / ((uint64_t)grid.x * grid.y)));
         if (+__start_simt_lds && +__stop_simt_lds > +__start_simt_lds)
             fill_random(__start_simt_lds, (size_t)(__stop_simt_lds - __start_simt_lds), g_rng);
         g_dyn.resize(dyn_bytes + 16);
         fill_random(g_dyn.data(), g_dyn.size(), g_rng);
+        if (log_lds) g_dyn_before = g_dyn;
         g_waves.assign(nwaves, Wave{});
         g_runnable.clear();
         g_bar_waiters.clear();
@@ -379,6 +391,11 @@ hipError_t run_grid(dim3 grid, dim3 block, size_t dyn_bytes, const std::function
             return hipErrorLaunchFailure;
         }
         g_items += nt;
+        if (log_lds) {
+            uint32_t changed = 0;
+            for (size_t i = 0; i < dyn_bytes; ++i) changed += g_dyn[i] != g_dyn_before[i];
+            g_lds_log.back().changed[bi] = changed;
+        }
     }
     g_body = nullptr;
     return hipSuccess;
@@ -424,6 +441,22 @@ void simt_memset_fault(uint64_t size, const uint32_t *words, uint64_t n_words) {
 void simt_block_order(int ordered) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     g_ordered = ordered != 0;
+}
+// TEST hook: simt_lds_log(1) empties the log of dynamic-LDS launches and starts it, (0) stops it;
+// simt_lds_log_get(g, ...) gives launch g's request in bytes and the first `cap` workgroups' changed
+// bytes, and returns its workgroup count (0: no such launch).
+void simt_lds_log(int on) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    g_lds_log_on = on != 0;
+    if (on) g_lds_log.clear();
+}
+uint64_t simt_lds_log_get(uint64_t g, uint64_t *dyn_bytes, uint32_t *changed, uint64_t cap) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (g >= g_lds_log.size()) return 0;
+    const LdsLog &l = g_lds_log[g];
+    *dyn_bytes = l.dyn_bytes;
+    for (uint64_t i = 0; i < l.changed.size() && i < cap; ++i) changed[i] = l.changed[i];
+    return l.changed.size();
 }
 void simt_stats(uint64_t *grids, uint64_t *items, uint64_t *switches) {
     *grids = g_grids;
