@@ -405,6 +405,40 @@ def _host_query(name: str, h, dt, patterns, reversed: bool, params: Optional[tup
     return n, out, loc_off, locs[:needed.value]
 
 
+def _load(name: str, call, position: Position, block: Optional[_Block], text_encoder, blob=None, table=None):
+    """What every load shares: the default block, an encoder class made an
+    instance, a host `blob` realigned to the block's vectors, the native
+    ``call(layout, arr, h, exp, act)``, the reference's two load errors, and
+    the table of an `EncodingTable` that has none yet recovered from the blob's
+    header (`table(offset)` reads its 256 bytes where the blob is not in host
+    memory).  Returns (handle, block, encoder, the blob as loaded)."""
+    block = block or blocks.Block2(Vector.U64)
+    if isinstance(text_encoder, type):
+        text_encoder = text_encoder.__new__(text_encoder)
+    arr = None
+    if blob is not None:
+        arr = blob if isinstance(blob, np.ndarray) else np.frombuffer(bytes(blob), dtype=np.uint8)
+        if arr.ctypes.data % block.ALIGN_SIZE:
+            a2 = aligned_buffer(arr.size, 16)
+            a2[:] = arr
+            arr = a2
+
+        def table(offset):
+            return bytes(arr[offset:][:256])
+
+    h = C.c_void_p()
+    exp, act = C.c_uint64(), C.c_uint64()
+    st = call(_layout(position, block, text_encoder), arr, C.byref(h), C.byref(exp), C.byref(act))
+    if st == _n.FMX_E_FORMAT:
+        raise InvalidFormat()
+    if st == _n.FMX_E_SIZE:
+        raise MismatchedBlobSize(exp.value, act.value)
+    _check(st, name)
+    if table and isinstance(text_encoder, text_encoders.EncodingTable) and not hasattr(text_encoder, "table"):
+        text_encoder.table = table(8 if block.ALIGN_SIZE == 8 else 16)
+    return h, block, text_encoder, arr
+
+
 # ----------------------------------------------------------------- FmIndex
 
 class FmIndex:
@@ -439,26 +473,10 @@ class FmIndex:
         (FMX_OPT_ROW_CONTEXT); `lut_rows` — single-row deep-table entries
         that hold the row's location (FMX_OPT_LUT_ROWS).  `options` overrides all
         (FMX_OPT_DERIVED: every derived structure)."""
-        block = block or blocks.Block2(Vector.U64)
-        if isinstance(text_encoder, type):
-            text_encoder = text_encoder.__new__(text_encoder)
-        arr = blob if isinstance(blob, np.ndarray) else np.frombuffer(bytes(blob), dtype=np.uint8)
-        if arr.ctypes.data % block.ALIGN_SIZE:
-            a2 = aligned_buffer(arr.size, 16)
-            a2[:] = arr
-            arr = a2
-        h = C.c_void_p()
-        exp, act = C.c_uint64(), C.c_uint64()
         mode = options if options is not None else _options(occ, deep_lut, full_sa, text, context, lut_rows)
-        st = _n.lib().fmx_load(_ptr(arr), arr.size, _layout(position, block, text_encoder), device, mode,
-                               C.byref(h), C.byref(exp), C.byref(act))
-        if st == _n.FMX_E_FORMAT:
-            raise InvalidFormat()
-        if st == _n.FMX_E_SIZE:
-            raise MismatchedBlobSize(exp.value, act.value)
-        _check(st, "fmx_load")
-        if isinstance(text_encoder, text_encoders.EncodingTable) and not hasattr(text_encoder, "table"):
-            text_encoder.table = bytes(arr[8 if block.ALIGN_SIZE == 8 else 16:][:256])
+        h, block, text_encoder, arr = _load(
+            "fmx_load", lambda layout, arr, *out: _n.lib().fmx_load(_ptr(arr), arr.size, layout, device, mode, *out),
+            position, block, text_encoder, blob=blob)
         return cls(h, position, block, text_encoder, arr)
 
     @classmethod
@@ -468,19 +486,11 @@ class FmIndex:
                     text: bool = False, context: bool = False, lut_rows: bool = False,
                     options: Optional[int] = None) -> "FmIndex":
         """Load a blob already resident in HBM (borrowed, must outlive the index)."""
-        block = block or blocks.Block2(Vector.U64)
-        if isinstance(text_encoder, type):
-            text_encoder = text_encoder.__new__(text_encoder)
-        h = C.c_void_p()
-        exp, act = C.c_uint64(), C.c_uint64()
         mode = options if options is not None else _options(occ, deep_lut, full_sa, text, context, lut_rows)
-        st = _n.lib().fmx_load_device(C.c_void_p(d_blob), blob_len, _layout(position, block, text_encoder),
-                                      device, mode, C.byref(h), C.byref(exp), C.byref(act))
-        if st == _n.FMX_E_FORMAT:
-            raise InvalidFormat()
-        if st == _n.FMX_E_SIZE:
-            raise MismatchedBlobSize(exp.value, act.value)
-        _check(st, "fmx_load_device")
+        h, block, text_encoder, _ = _load(
+            "fmx_load_device",
+            lambda layout, _, *out: _n.lib().fmx_load_device(C.c_void_p(d_blob), blob_len, layout, device, mode, *out),
+            position, block, text_encoder)
         return cls(h, position, block, text_encoder, None)
 
     @classmethod
@@ -495,25 +505,20 @@ class FmIndex:
         then the body is read in pinned chunks overlapped with their DMA.
         `direct`: the body is read with O_DIRECT (FMX_LOAD_DIRECT), bypassing
         the page cache — a cold load (raises if the file system refuses it)."""
-        block = block or blocks.Block2(Vector.U64)
-        if isinstance(text_encoder, type):
-            text_encoder = text_encoder.__new__(text_encoder)
-        h = C.c_void_p()
-        exp, act = C.c_uint64(), C.c_uint64()
         mode = options if options is not None else _options(occ, deep_lut, full_sa, text, context, lut_rows)
         if direct:
             mode |= _n.FMX_LOAD_DIRECT
-        st = _n.lib().fmx_load_file(os.fsencode(path), _layout(position, block, text_encoder), device, mode,
-                                    int(chunk_bytes), C.byref(h), C.byref(exp), C.byref(act))
-        if st == _n.FMX_E_FORMAT:
-            raise InvalidFormat()
-        if st == _n.FMX_E_SIZE:
-            raise MismatchedBlobSize(exp.value, act.value)
-        _check(st, f"fmx_load_file({path})")
-        if isinstance(text_encoder, text_encoders.EncodingTable) and not hasattr(text_encoder, "table"):
+
+        def table(offset):
             with open(path, "rb") as f:
-                f.seek(8 if block.ALIGN_SIZE == 8 else 16)
-                text_encoder.table = f.read(256)
+                f.seek(offset)
+                return f.read(256)
+
+        h, block, text_encoder, _ = _load(
+            f"fmx_load_file({path})",
+            lambda layout, _, *out: _n.lib().fmx_load_file(os.fsencode(path), layout, device, mode, int(chunk_bytes),
+                                                           *out),
+            position, block, text_encoder, table=table)
         return cls(h, position, block, text_encoder, None)
 
     def close(self):
@@ -865,24 +870,11 @@ class MultiDeviceIndex:
 
     def __init__(self, blob, devices: Sequence[int], position: Position = u32, block: Optional[_Block] = None,
                  text_encoder=text_encoders.EncodingTable, options: int = _n.FMX_OPT_DEFAULT):
-        block = block or blocks.Block2(Vector.U64)
-        if isinstance(text_encoder, type):
-            text_encoder = text_encoder.__new__(text_encoder)
-        arr = blob if isinstance(blob, np.ndarray) else np.frombuffer(bytes(blob), dtype=np.uint8)
-        if arr.ctypes.data % block.ALIGN_SIZE:
-            a2 = aligned_buffer(arr.size, 16)
-            a2[:] = arr
-            arr = a2
         devs = (C.c_int * len(devices))(*devices)
-        h = C.c_void_p()
-        exp, act = C.c_uint64(), C.c_uint64()
-        st = _n.lib().fmx_multi_load(_ptr(arr), arr.size, _layout(position, block, text_encoder), devs, len(devices),
-                                     options, C.byref(h), C.byref(exp), C.byref(act))
-        if st == _n.FMX_E_FORMAT:
-            raise InvalidFormat()
-        if st == _n.FMX_E_SIZE:
-            raise MismatchedBlobSize(exp.value, act.value)
-        _check(st, "fmx_multi_load")
+        h = _load("fmx_multi_load",
+                  lambda layout, arr, *out: _n.lib().fmx_multi_load(_ptr(arr), arr.size, layout, devs, len(devices),
+                                                                    options, *out),
+                  position, block, text_encoder, blob=blob)[0]
         self._h = h
         self._dt = position.dtype
         self.devices = list(devices)

@@ -33,7 +33,7 @@ static bool layout_valid(const fmx_layout &L) {
 }
 
 // Vector::ALIGN_SIZE (blocks/vector.rs:16,31,46): 8 for u32/u64, 16 for u128.
-static uint64_t align_of(const fmx_layout &L) { return L.vec_bits == 128 ? 16 : 8; }
+uint64_t align_of(const fmx_layout &L) { return L.vec_bits == 128 ? 16 : 8; }
 
 static uint64_t read_p(const uint8_t *p, uint32_t pb) {
     if (pb == 4) { uint32_t v; memcpy(&v, p, 4); return v; }
@@ -228,41 +228,26 @@ static void harvest_spans(fmx_index *ix) {
     ix->spans.erase(ix->spans.begin() + keep, ix->spans.begin() + look);
 }
 
-// Bracket one launch with events on its stream when timing is on.
+// Bracket one launch with events on its stream when timing is on: the timer
+// `name`.  With `first` and `second` — a locate launch — a third event goes
+// between its two kernels (launch(mid) records it; mid null: not timed): the
+// timers `first` (k_search) and `second` (k_emit) as well.
 template <class F>
-static hipError_t timed(fmx_index *ix, const char *name, hipStream_t s, uint64_t units, F &&launch) {
-    std::unique_lock<std::mutex> g(ix->timing_mu);
-    if (!ix->timing || (ix->timing_seq++ % ix->timing_every) != 0) {
-        g.unlock();
-        return launch();
-    }
-    harvest_spans(ix);
-    hipEvent_t a = take_event(ix), b = take_event(ix);
-    if (!a || !b) return hipErrorOutOfMemory;
-    hipEventRecord(a, s);
-    hipError_t e = launch();
-    hipEventRecord(b, s);
-    ix->spans.push_back(TimedSpan{a, nullptr, b, {timer(ix, name), -1, -1}, units});
-    return e;
-}
-
-// The same for a locate launch, with a third event between its two kernels:
-// timers `name` (the launch), `first` (k_search) and `second` (k_emit).
-template <class F>
-static hipError_t timed_split(fmx_index *ix, const char *name, const char *first, const char *second, hipStream_t s,
-                              uint64_t units, F &&launch) {
+static hipError_t timed(fmx_index *ix, const char *name, hipStream_t s, uint64_t units, F &&launch,
+                        const char *first = nullptr, const char *second = nullptr) {
     std::unique_lock<std::mutex> g(ix->timing_mu);
     if (!ix->timing || (ix->timing_seq++ % ix->timing_every) != 0) {
         g.unlock();
         return launch(nullptr);
     }
     harvest_spans(ix);
-    hipEvent_t a = take_event(ix), m = take_event(ix), b = take_event(ix);
-    if (!a || !m || !b) return hipErrorOutOfMemory;
+    hipEvent_t a = take_event(ix), m = first ? take_event(ix) : nullptr, b = take_event(ix);
+    if (!a || (first && !m) || !b) return hipErrorOutOfMemory;
     hipEventRecord(a, s);
     hipError_t e = launch(m);
     hipEventRecord(b, s);
-    ix->spans.push_back(TimedSpan{a, m, b, {timer(ix, name), timer(ix, first), timer(ix, second)}, units});
+    ix->spans.push_back(TimedSpan{a, m, b, {timer(ix, name), first ? timer(ix, first) : -1,
+                                            second ? timer(ix, second) : -1}, units});
     return e;
 }
 
@@ -273,33 +258,6 @@ static fmx_status dev_err(hipError_t e) {
     if (debug) fprintf(stderr, "fmx: HIP error %d (%s)\n", (int)e, hipGetErrorString(e));
     return FMX_E_DEVICE;
 }
-
-// Makes the index's device current for one entry point and restores the
-// caller's current device on every return path.
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = false;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        ok = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) hipSetDevice(prev);
-    }
-};
-
-// FMX_LOAD_TRACE=1: each load stage's wall time on stderr.
-struct LoadTrace {
-    bool on = getenv("FMX_LOAD_TRACE") != nullptr;
-    std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
-    void mark(const char *what) {
-        if (!on) return;
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[fmx load] %-22s %9.3f ms\n", what,
-                std::chrono::duration<double, std::milli>(now - t).count());
-        t = now;
-    }
-};
 
 // The status word of `s`: every stream an index launches on gets a device
 // word of its own, so fmx_sync(s) reads and clears only what that stream's
@@ -407,6 +365,14 @@ static fmx_status with_status(fmx_index *ix, hipStream_t s, F &&launch) {
     const fmx_status st = launch(status);
     status_launched(ix, idx, s);
     return st;
+}
+
+// One launch, `launch(status)`, under the stream's status word and the timer `name`.
+template <class F>
+static fmx_status timed_launch(fmx_index *ix, const char *name, hipStream_t s, uint64_t units, F &&launch) {
+    return with_status(ix, s, [&](uint32_t *status) {
+        return dev_err(timed(ix, name, s, units, [&](hipEvent_t) { return launch(status); }));
+    });
 }
 
 static fmx_status ensure_scratch(fmx_index *ix, uint64_t bytes) {
@@ -788,6 +754,40 @@ static fmx_status finish_load(fmx_index *ix, uint32_t options) {
     return FMX_OK;
 }
 
+BlobReader host_reader(const uint8_t *blob, uint64_t blob_len) {
+    return [=](uint64_t off, uint64_t len, void *dst) {
+        if (off + len > blob_len) return false;
+        memcpy(dst, blob + off, len);
+        return true;
+    };
+}
+
+fmx_status load_index(const BlobReader &rd, uint64_t blob_len, fmx_layout layout, int device, uint32_t options,
+                      const PlaceBlob &place, fmx_index **out, uint64_t *expected_total, uint64_t *actual_total) {
+    LoadTrace tr;
+    BlobView bv;
+    fmx_status st = parse_blob(rd, blob_len, layout, &bv, expected_total, actual_total);
+    if (st || !place) return st;
+    tr.mark("parse headers");
+    DeviceGuard dg(device);
+    if (!dg.ok) return FMX_E_DEVICE;
+    tr.mark("device (first HIP call)");
+    fmx_index *ix = new (std::nothrow) fmx_index();
+    if (!ix) return FMX_E_DEVICE;
+    ix->bv = bv;
+    ix->device = device;
+    ix->blob_len = blob_len;
+    st = place(ix, tr);
+    if (!st) st = finish_load(ix, options);
+    if (st) {
+        fmx_free(ix);
+        return st;
+    }
+    tr.mark("finish_load");
+    *out = ix;
+    return FMX_OK;
+}
+
 static fmx_status read_status(fmx_index *ix, hipStream_t s) {
     int idx;
     {
@@ -872,57 +872,28 @@ fmx_status fmx_load(const uint8_t *blob, uint64_t blob_len, fmx_layout layout, i
     *out = nullptr;
     if (!layout_valid(layout)) return FMX_E_LAYOUT;
     if (((uintptr_t)blob) % align_of(layout) != 0) return FMX_E_ALIGN;  // zerocopy alignment panic
-    BlobView bv;
-    BlobReader rd = [&](uint64_t off, uint64_t len, void *dst) {
-        if (off + len > blob_len) return false;
-        memcpy(dst, blob + off, len);
-        return true;
-    };
-    LoadTrace tr;
-    fmx_status st = parse_blob(rd, blob_len, layout, &bv, expected_total, actual_total);
-    if (st) return st;
-    tr.mark("parse headers");
-    DeviceGuard dg(device);
-    if (!dg.ok) return FMX_E_DEVICE;
-    tr.mark("device (first HIP call)");
-    fmx_index *ix = new (std::nothrow) fmx_index();
-    if (!ix) return FMX_E_DEVICE;
-    ix->bv = bv;
-    ix->device = device;
-    ix->host_blob = blob;
-    ix->blob_len = blob_len;
-    if (hipMalloc(&ix->d_blob_owned, blob_len) != hipSuccess) {
-        fmx_free(ix);
-        return FMX_E_DEVICE;
-    }
-    tr.mark("hipMalloc blob");
-    // On the index's own stream, waited for: a plain hipMemcpy from pageable
-    // memory may return before its DMA lands, and the load's kernels (the
-    // record re-layout reads the blob) run on this non-blocking stream, which
-    // is not ordered after the null stream — they could read the allocation's
-    // previous contents (intermittent wrong counts with
-    // interleaved records only; reproduced by tests/test_simt.py).  Through a
-    // pinned stage of its own (32 MiB chunks, freed after the load): no DMA
-    // reads the caller's pageable blob (round 4).
-    if (hipStreamCreateWithFlags(&ix->stream, hipStreamNonBlocking) != hipSuccess) {
-        fmx_free(ix);
-        return FMX_E_DEVICE;
-    }
-    {
+    return load_index(host_reader(blob, blob_len), blob_len, layout, device, options,
+                      [&](fmx_index *ix, LoadTrace &tr) {
+        ix->host_blob = blob;
+        if (hipMalloc(&ix->d_blob_owned, blob_len) != hipSuccess) return FMX_E_DEVICE;
+        tr.mark("hipMalloc blob");
+        // On the index's own stream, waited for: a plain hipMemcpy from pageable
+        // memory may return before its DMA lands, and the load's kernels (the
+        // record re-layout reads the blob) run on this non-blocking stream, which
+        // is not ordered after the null stream — they could read the allocation's
+        // previous contents (intermittent wrong counts with
+        // interleaved records only; reproduced by tests/test_simt.py).  Through a
+        // pinned stage of its own (32 MiB chunks, freed after the load): no DMA
+        // reads the caller's pageable blob (round 4).
+        if (hipStreamCreateWithFlags(&ix->stream, hipStreamNonBlocking) != hipSuccess) return FMX_E_DEVICE;
         Stage up(32ull << 20);
         if (up.h2d(ix->d_blob_owned, blob, blob_len, ix->stream) != hipSuccess ||
-            hipStreamSynchronize(ix->stream) != hipSuccess) {
-            fmx_free(ix);
+            hipStreamSynchronize(ix->stream) != hipSuccess)
             return FMX_E_DEVICE;
-        }
-    }
-    tr.mark("host -> HBM");
-    ix->d_blob = ix->d_blob_owned;
-    st = finish_load(ix, options);
-    if (st) { fmx_free(ix); return st; }
-    tr.mark("finish_load");
-    *out = ix;
-    return FMX_OK;
+        tr.mark("host -> HBM");
+        ix->d_blob = ix->d_blob_owned;
+        return FMX_OK;
+    }, out, expected_total, actual_total);
 }
 
 fmx_status fmx_load_device(const uint8_t *d_blob, uint64_t blob_len, fmx_layout layout, int device,
@@ -931,27 +902,16 @@ fmx_status fmx_load_device(const uint8_t *d_blob, uint64_t blob_len, fmx_layout 
     *out = nullptr;
     if (!layout_valid(layout)) return FMX_E_LAYOUT;
     if (((uintptr_t)d_blob) % align_of(layout) != 0) return FMX_E_ALIGN;
-    DeviceGuard dg(device);
+    DeviceGuard dg(device);  // (the header reads below need the device)
     if (!dg.ok) return FMX_E_DEVICE;
     if (hipDeviceSynchronize() != hipSuccess) return FMX_E_DEVICE;  // the blob's writers, on any stream
-    BlobView bv;
     Stage hdr(64 << 10);  // the header reads land in pinned memory, then in the parser's locals
-    BlobReader rd = [&](uint64_t off, uint64_t len, void *dst) {
-        if (off + len > blob_len) return false;
-        return hdr.d2h(dst, d_blob + off, len, nullptr) == hipSuccess;
-    };
-    fmx_status st = parse_blob(rd, blob_len, layout, &bv, expected_total, actual_total);
-    if (st) return st;
-    fmx_index *ix = new (std::nothrow) fmx_index();
-    if (!ix) return FMX_E_DEVICE;
-    ix->bv = bv;
-    ix->device = device;
-    ix->blob_len = blob_len;
-    ix->d_blob = d_blob;
-    st = finish_load(ix, options);
-    if (st) { fmx_free(ix); return st; }
-    *out = ix;
-    return FMX_OK;
+    return load_index([&](uint64_t off, uint64_t len, void *dst) {
+        return off + len <= blob_len && hdr.d2h(dst, d_blob + off, len, nullptr) == hipSuccess;
+    }, blob_len, layout, device, options, [&](fmx_index *ix, LoadTrace &) {
+        ix->d_blob = d_blob;
+        return FMX_OK;
+    }, out, expected_total, actual_total);
 }
 
 // Streamed file ingest: pread into two pinned chunks, each handed to the DMA
@@ -1059,39 +1019,20 @@ fmx_status fmx_load_file(const char *path, fmx_layout layout, int device, uint32
     struct stat sb;
     if (fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode)) { close_all(); return FMX_E_ARG; }
     const uint64_t blob_len = (uint64_t)sb.st_size;
-    LoadTrace tr;
-    BlobView bv;
-    BlobReader rd = [&](uint64_t off, uint64_t len, void *dst) {
+    const fmx_status st = load_index([&](uint64_t off, uint64_t len, void *dst) {
         return off + len <= blob_len && read_full(fd, off, len, dst);
-    };
-    fmx_status st = parse_blob(rd, blob_len, layout, &bv, expected_total, actual_total);
-    if (st) { close_all(); return st; }
-    tr.mark("parse headers");
-    DeviceGuard dg(device);
-    if (!dg.ok) { close_all(); return FMX_E_DEVICE; }
-    tr.mark("device (first HIP call)");
-    fmx_index *ix = new (std::nothrow) fmx_index();
-    if (!ix) { close_all(); return FMX_E_DEVICE; }
-    ix->bv = bv;
-    ix->device = device;
-    ix->blob_len = blob_len;
-    if (hipMalloc(&ix->d_blob_owned, std::max<uint64_t>(blob_len, 1)) != hipSuccess) {
-        close_all();
-        fmx_free(ix);
-        return FMX_E_DEVICE;
-    }
-    tr.mark("hipMalloc blob");
-    const uint64_t chunk = chunk_bytes ? align_up(chunk_bytes, 4096) : (16ull << 20);
-    st = stream_file(direct ? dfd : fd, blob_len, ix->d_blob_owned, chunk, direct);
+    }, blob_len, layout, device, options, [&](fmx_index *ix, LoadTrace &tr) {
+        if (hipMalloc(&ix->d_blob_owned, std::max<uint64_t>(blob_len, 1)) != hipSuccess) return FMX_E_DEVICE;
+        tr.mark("hipMalloc blob");
+        const uint64_t chunk = chunk_bytes ? align_up(chunk_bytes, 4096) : (16ull << 20);
+        const fmx_status fs = stream_file(direct ? dfd : fd, blob_len, ix->d_blob_owned, chunk, direct);
+        if (fs) return fs;
+        tr.mark(direct ? "file -> HBM (O_DIRECT)" : "file -> HBM");
+        ix->d_blob = ix->d_blob_owned;
+        return FMX_OK;
+    }, out, expected_total, actual_total);
     close_all();
-    if (st) { fmx_free(ix); return st; }
-    tr.mark(direct ? "file -> HBM (O_DIRECT)" : "file -> HBM");
-    ix->d_blob = ix->d_blob_owned;
-    st = finish_load(ix, options);
-    if (st) { fmx_free(ix); return st; }
-    tr.mark("finish_load");
-    *out = ix;
-    return FMX_OK;
+    return st;
 }
 
 void fmx_free(fmx_index *ix) {
@@ -1203,10 +1144,8 @@ fmx_status fmx_count_batch_async(fmx_index *ix, const uint8_t *d_bytes, const ui
     if (!ix || (flags & kStrandFlags) || (n && (!d_bytes || !d_offsets || !d_counts))) return FMX_E_ARG;
     hipStream_t s = stream ? (hipStream_t)stream : ix->stream;
     DeviceGuard dg(ix->device);
-    return with_status(ix, s, [&](uint32_t *status) {
-        return dev_err(timed(ix, "count", s, n, [&] {
-            return launch_count(ix, d_bytes, d_offsets, n, flags, d_counts, status, s);
-        }));
+    return timed_launch(ix, "count", s, n, [&](uint32_t *status) {
+        return launch_count(ix, d_bytes, d_offsets, n, flags, d_counts, status, s);
     });
 }
 
@@ -1241,22 +1180,30 @@ static hipError_t zero_locs(uint64_t *d_loc_offsets, uint64_t *d_needed, hipStre
     return e == hipSuccess ? hipMemsetAsync(d_needed, 0, 8, s) : e;
 }
 
+// A locate job's arguments (its stream and `reserved` apart): the outputs, the
+// patterns of a batch that has any, no strand flag, and a workspace of the
+// batch's size — of an empty batch's too only where `sized_empty` asks.
+static bool locate_job_ok(const fmx_index *ix, const fmx_locate_job &j, bool sized_empty) {
+    if (!j.d_loc_offsets || !j.d_needed || (j.n_patterns && (!j.d_bytes || !j.d_offsets)) || (j.cap && !j.d_locs))
+        return false;
+    if ((j.flags & kStrandFlags) || !ws_ok(j.d_workspace, j.workspace_bytes)) return false;
+    return (j.n_patterns == 0 && !sized_empty) || j.workspace_bytes >= ws_bytes_for(ix, j.n_patterns);
+}
+
 fmx_status fmx_locate_batch_async(fmx_index *ix, const uint8_t *d_bytes, const uint64_t *d_offsets, uint64_t n,
                                   uint32_t flags, void *d_counts, uint64_t *d_loc_offsets, void *d_locs,
                                   uint64_t cap, uint64_t *d_needed, void *d_ws, uint64_t ws_bytes, void *stream) {
-    if (!ix || !d_loc_offsets || !d_needed || (n && (!d_bytes || !d_offsets)) || (cap && !d_locs)) return FMX_E_ARG;
-    if ((flags & kStrandFlags) || !ws_ok(d_ws, ws_bytes)) return FMX_E_ARG;
+    const fmx_locate_job j{d_bytes, d_offsets, n,        flags, 0,        d_counts, d_loc_offsets,
+                           d_locs,  cap,       d_needed, d_ws,  ws_bytes, stream};
+    if (!ix || !locate_job_ok(ix, j, false)) return FMX_E_ARG;
     hipStream_t s = stream ? (hipStream_t)stream : ix->stream;
     DeviceGuard dg(ix->device);
     if (n == 0) return dev_err(zero_locs(d_loc_offsets, d_needed, s));
-    if (ws_bytes < ws_bytes_for(ix, n)) return FMX_E_ARG;
     uint8_t *ws = (uint8_t *)d_ws;
     const uint64_t G = locate_tiles_cap(n);
-    return with_status(ix, s, [&](uint32_t *status) {
-        return dev_err(timed(ix, "locate", s, n, [&] {
-            return launch_locate(ix, d_bytes, d_offsets, n, flags, d_counts, d_loc_offsets, d_locs, cap, d_needed,
-                                 (uint64_t *)(ws + kWsHeader), G, status, s);
-        }));
+    return timed_launch(ix, "locate", s, n, [&](uint32_t *status) {
+        return launch_locate(ix, d_bytes, d_offsets, n, flags, d_counts, d_loc_offsets, d_locs, cap, d_needed,
+                             (uint64_t *)(ws + kWsHeader), G, status, s);
     });
 }
 
@@ -1287,9 +1234,7 @@ static fmx_status slot_query(fmx_index *ix, const char *name, uint64_t n, uint64
     if (n == 0) return loc ? dev_err(zero_locs(d_loc_offsets, d_needed, s)) : FMX_OK;
     const LocOut out{d_loc_offsets, d_locs, cap, d_needed, loc ? (uint64_t *)((uint8_t *)d_ws + kWsHeader) : nullptr,
                      locate_tiles_cap(slots)};
-    return with_status(ix, s, [&](uint32_t *status) {
-        return dev_err(timed(ix, name, s, slots, [&] { return launch(out, status, s); }));
-    });
+    return timed_launch(ix, name, s, slots, [&](uint32_t *status) { return launch(out, status, s); });
 }
 }
 
@@ -1358,10 +1303,7 @@ fmx_status fmx_locate_group_async(fmx_index *ix, const fmx_locate_job *jobs, uin
     hipStream_t s = stream ? (hipStream_t)stream : ix->stream;
     for (uint64_t i = 0; i < n_jobs; ++i) {
         const fmx_locate_job &j = jobs[i];
-        if (!j.d_loc_offsets || !j.d_needed || (j.n_patterns && (!j.d_bytes || !j.d_offsets)) ||
-            (j.cap && !j.d_locs) || !j.d_workspace || j.workspace_bytes < ws_bytes_for(ix, j.n_patterns) ||
-            ((uintptr_t)j.d_workspace & 15) != 0 || j.reserved != 0 || (j.flags & kStrandFlags))
-            return FMX_E_ARG;
+        if (!locate_job_ok(ix, j, true) || j.reserved != 0) return FMX_E_ARG;
         for (uint64_t k = 0; k < i; ++k)
             if (jobs[k].d_workspace == j.d_workspace) return FMX_E_ARG;  // the batches run concurrently
     }
@@ -1406,10 +1348,9 @@ fmx_status fmx_locate_group_async(fmx_index *ix, const fmx_locate_job *jobs, uin
         }
         if (grps[0].n == 0) continue;
         const uint32_t ngroups = grps[ng].n ? ng + 1 : ng;
-        const fmx_status st = dev_err(timed_split(ix, "locate", "locate.search", "locate.emit", s, units,
-                                                  [&](hipEvent_t mid) {
+        const fmx_status st = dev_err(timed(ix, "locate", s, units, [&](hipEvent_t mid) {
             return launch_locate_groups(ix, grps.get(), ngroups, stage, status, s, mid);
-        }));
+        }, "locate.search", "locate.emit"));
         if (st) return st;
     }
     return FMX_OK;
@@ -1468,30 +1409,6 @@ static uint32_t stage_hint(const uint64_t *offsets, uint64_t n, uint32_t flags =
     bool fixed = m <= 0xffffu;
     for (uint64_t i = 1; fixed && i < n; ++i) fixed = offsets[i + 1] - offsets[i] == m;
     return FMX_HINT_STAGE_KB(kb) | (fixed ? FMX_HINT_FIXED_LEN(m) : 0u);
-}
-
-fmx_status fmx_count_batch(fmx_index *ix, const uint8_t *bytes, const uint64_t *offsets, uint64_t n,
-                           uint32_t flags, void *out_counts) {
-    if (!ix || (flags & kStrandFlags) || (n && (!offsets || !out_counts))) return FMX_E_ARG;
-    if (n == 0) return FMX_OK;
-    std::lock_guard<std::mutex> g(ix->mu);
-    fmx_status st = check_patterns(offsets, n);
-    if (st) return st;
-    DeviceGuard dg(ix->device);
-    const uint64_t nb = offsets[n], pb = ix->bv.L.pos_bytes;
-    const uint64_t o_off = align_up(nb, 256), o_cnt = o_off + align_up((n + 1) * 8, 256);
-    st = ensure_scratch(ix, o_cnt + n * pb);
-    if (st) return st;
-    hipStream_t s = ix->stream;
-    uint8_t *d = ix->d_scratch;
-    hipError_t e = ix->stage.h2d(d, bytes, nb, s);
-    if (e == hipSuccess) e = ix->stage.h2d(d + o_off, offsets, (n + 1) * 8, s);
-    if (e != hipSuccess) return FMX_E_DEVICE;
-    flags = (flags & 0xffu) | stage_hint(offsets, n);
-    st = fmx_count_batch_async(ix, d, (uint64_t *)(d + o_off), n, flags, d + o_cnt, s);
-    if (st) return st;
-    if (ix->stage.d2h(out_counts, d + o_cnt, n * pb, s) != hipSuccess) return FMX_E_DEVICE;
-    return read_status(ix, s);
 }
 
 // The host-API locate workspace lives in the index.  Not initialised: every
@@ -1606,6 +1523,21 @@ static fmx_status host_query(fmx_index *ix, Carve &c, const uint8_t *bytes, cons
     }
     return FMX_E_DEVICE;
 }
+}
+
+// Counts: one output, no locations; an empty pattern is an error, as for fmx_locate_batch.
+fmx_status fmx_count_batch(fmx_index *ix, const uint8_t *bytes, const uint64_t *offsets, uint64_t n,
+                           uint32_t flags, void *out_counts) {
+    if (!ix || (flags & kStrandFlags) || (n && (!offsets || !out_counts))) return FMX_E_ARG;
+    if (n == 0) return FMX_OK;
+    const fmx_status st = check_patterns(offsets, n);
+    if (st) return st;
+    Carve c(offsets, n, flags);
+    const uint64_t o_cnt = c.add(n * ix->bv.L.pos_bytes, out_counts);
+    return host_query(ix, c, bytes, offsets, n, n, false, nullptr, nullptr, 0, nullptr,
+                      [&](uint8_t *d, uint64_t, hipStream_t s) {
+                          return fmx_count_batch_async(ix, d, (uint64_t *)(d + c.o_off), n, c.flags, d + o_cnt, s);
+                      });
 }
 
 fmx_status fmx_locate_batch(fmx_index *ix, const uint8_t *bytes, const uint64_t *offsets, uint64_t n,

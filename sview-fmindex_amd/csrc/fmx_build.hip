@@ -55,7 +55,7 @@ struct DBuf {
 };
 
 static unsigned grid_of(uint64_t n, unsigned cap = 1u << 20) {
-    uint64_t g = (n + 255) / 256;
+    uint64_t g = tiles_of(n);
     if (g == 0) g = 1;
     return (unsigned)(g < cap ? g : cap);
 }

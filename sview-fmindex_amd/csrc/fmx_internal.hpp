@@ -5,7 +5,10 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <chrono>
 #include <cstdint>
+#include <cstdio>
+#include <cstdlib>
 #include <deque>
 #include <functional>
 #include <memory>
@@ -28,6 +31,8 @@ constexpr int kMaxSigma = 64;  // Block6 indexes at most 2^6 symbols (blocks/blo
 constexpr int kMaxK = 40;      // W^k must fit the u32 header field anyway (count_array.rs:68)
 constexpr int kStageBytes = 16384;      // LDS bytes for a workgroup's 256 patterns (else read from HBM)
 constexpr int kStageBytesLong = 57344;  // the same with FMX_HINT_LONG_PATTERNS
+// The 256-pattern (256-slot, 256-thread) tiles that hold n.
+constexpr uint64_t tiles_of(uint64_t n) { return (n + 255) / 256; }
 
 // Parsed blob headers.  Field-for-field what FmIndex::load derives
 // (src/load_from_blob.rs:28-85); offsets are byte offsets into the blob.
@@ -50,6 +55,24 @@ using BlobReader = std::function<bool(uint64_t off, uint64_t len, void *dst)>;
 
 fmx_status parse_blob(const BlobReader &rd, uint64_t blob_len, fmx_layout L, BlobView *out,
                       uint64_t *expected_total, uint64_t *actual_total);
+// The alignment a layout's blob needs in host memory and in HBM (Vector::ALIGN_SIZE).
+uint64_t align_of(const fmx_layout &L);
+// A blob in host memory as a BlobReader.
+BlobReader host_reader(const uint8_t *blob, uint64_t blob_len);
+
+// Makes `dev` current for one entry point (without `dev`: leaves the current
+// device alone) and restores the caller's current device on every return path.
+struct DeviceGuard {
+    int prev = -1;
+    bool ok = true;
+    DeviceGuard() {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    }
+    explicit DeviceGuard(int dev) : DeviceGuard() { ok = hipSetDevice(dev) == hipSuccess; }
+    ~DeviceGuard() {
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+};
 
 // Blob section sizes for the builder (FmIndexBuilder::blob_size, builder/mod.rs:165-181).
 struct BlobSizes {
@@ -285,6 +308,28 @@ struct fmx_index {
 };
 
 namespace fmx {
+
+// FMX_LOAD_TRACE=1: each load stage's wall time on stderr.
+struct LoadTrace {
+    bool on = getenv("FMX_LOAD_TRACE") != nullptr;
+    std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+    void mark(const char *what) {
+        if (!on) return;
+        const auto now = std::chrono::steady_clock::now();
+        fprintf(stderr, "[fmx load] %-22s %9.3f ms\n", what,
+                std::chrono::duration<double, std::milli>(now - t).count());
+        t = now;
+    }
+};
+
+// Every load (fmx_api.cpp): the blob of blob_len bytes behind `rd` validated
+// (parse_blob), then — on `device` — the index made, `place` putting the blob
+// in HBM (it sets ix->d_blob, and d_blob_owned when the index owns the copy)
+// and the load finished; the index is freed on every failure.  `place` null:
+// validation only, no device touched and *out left alone (fmx_multi_load).
+using PlaceBlob = std::function<fmx_status(fmx_index *ix, LoadTrace &tr)>;
+fmx_status load_index(const BlobReader &rd, uint64_t blob_len, fmx_layout layout, int device, uint32_t options,
+                      const PlaceBlob &place, fmx_index **out, uint64_t *expected_total, uint64_t *actual_total);
 
 // Query launchers (fmx_query.hip).  All asynchronous on `stream`.
 hipError_t launch_count(const fmx_index *ix, const uint8_t *d_bytes, const uint64_t *d_offsets, uint64_t n,
@@ -545,7 +590,7 @@ struct GroupTab {
 };
 constexpr uint64_t kWsGroupTab = 256 + 4ull * kGroupBins;  // (16-B aligned)
 constexpr uint64_t kWsHeader = kWsGroupTab + ((sizeof(GroupTab) + 15) & ~15ull);
-inline uint64_t group_chunks(uint64_t n) { return ((n + 255) / 256 + kGroupChunkTiles - 1) / kGroupChunkTiles; }
+inline uint64_t group_chunks(uint64_t n) { return (tiles_of(n) + kGroupChunkTiles - 1) / kGroupChunkTiles; }
 
 // The kernels that depend on the occ layout, one table per (P, N) pair
 // (fmx_layout.hip, one translation unit per pair); vb = V bits, rec = 0

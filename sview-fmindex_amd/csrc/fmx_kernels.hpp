@@ -15,14 +15,14 @@
 
 namespace fmx {
 
-static inline unsigned grid_for(uint64_t threads) { return (unsigned)((threads + 255) / 256); }
+static inline unsigned grid_for(uint64_t threads) { return (unsigned)tiles_of(threads); }
 // k_dlut_level: one thread per parent up to 2^24 workgroups, then grid-stride
 static inline unsigned grid_dlut(uint64_t np) {
-    const uint64_t g = (np + 255) / 256;
+    const uint64_t g = tiles_of(np);
     return (unsigned)(g < (1ull << 24) ? (g ? g : 1) : (1ull << 24) - 1);
 }
 static inline unsigned grid_stride_for(uint64_t n) {
-    const uint64_t g = (n + 255) / 256;
+    const uint64_t g = tiles_of(n);
     return (unsigned)(g < 65536 ? (g ? g : 1) : 65536);
 }
 
@@ -72,6 +72,49 @@ __device__ __forceinline__ uint64_t block_excl_scan(uint64_t v, uint64_t *total,
 
 // ----------------------------------------------------------------- k_count
 
+// The staging loop of every query kernel: the span [b0, b0 + len32) of `bytes`
+// into LDS as encoded symbols, through 16-B vectors aligned by ADDRESS
+// (d_bytes itself may have any alignment): the first vector holds the span's
+// first byte, the last one its last byte, up to four per thread in flight.
+// Positions within the span are 32-bit (len32 <= stage_bytes): byte w of
+// vector v is span byte 16 v + w - lead, kept if below len32 (unsigned).  `at`
+// is the byte's place in pattern order (a reversed input range is stored
+// reversed).  Unless ST is kStrandRc the forward copy goes through enc to
+// s_fw[at]; unless ST is kStrandNone the other strand goes through s_rc to the
+// mirror image s_bw[len32 - 1 - at] (strand_pattern).
+template <int ST>
+__device__ __forceinline__ void stage_span(const uint8_t *enc, const uint8_t *s_rc, uint8_t *s_fw, uint8_t *s_bw,
+                                           const uint8_t *bytes, uint64_t b0, uint32_t len32, bool rev) {
+    using V4 = uint32_t __attribute__((ext_vector_type(4)));
+    const uint64_t addr = reinterpret_cast<uint64_t>(bytes) + b0, a0 = addr & ~15ull;
+    const uint32_t lead = (uint32_t)(addr - a0);
+    const uint32_t nv = len32 ? (lead + len32 + 15) >> 4 : 0u;  // (an empty span: no vector holds a byte of it)
+    const V4 *src = reinterpret_cast<const V4 *>(a0);
+    for (uint32_t v0 = 0; v0 < nv; v0 += 4 * 256) {
+        V4 x[4];
+#pragma unroll
+        for (uint32_t u = 0; u < 4; ++u) {
+            const uint32_t v = v0 + u * 256 + threadIdx.x;
+            if (v < nv) x[u] = src[v];
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < 4; ++u) {
+            const uint32_t v = v0 + u * 256 + threadIdx.x;
+            if (v >= nv) continue;
+            const uint32_t base = 16u * v - lead;
+#pragma unroll
+            for (uint32_t w = 0; w < 16; ++w) {
+                const uint32_t x0 = base + w;
+                if (x0 >= len32) continue;
+                const uint32_t c = (x[u][w >> 2] >> (8 * (w & 3))) & 0xffu;
+                const uint32_t at = rev ? len32 - 1u - x0 : x0;
+                if (ST != kStrandRc) s_fw[at] = enc[c];
+                if (ST != kStrandNone) s_bw[len32 - 1u - at] = s_rc[c];
+            }
+        }
+    }
+}
+
 // Stage the workgroup's patterns [first, first+256) as encoded symbols in
 // LDS (pattern order; a reversed input range is stored reversed, which puts
 // every pattern back in pattern order).  One round trip for the offsets (each
@@ -112,35 +155,7 @@ __device__ __forceinline__ bool stage_patterns(const Tables<P> &s, uint8_t *s_pa
         if (bad_stride) atomicOr(status, kStatusStride);
         return false;
     }
-    using V4 = uint32_t __attribute__((ext_vector_type(4)));
-    // aligned by ADDRESS (d_bytes itself may have any alignment): the first
-    // vector holds the span's first byte, the last one its last byte
-    const uint64_t addr = reinterpret_cast<uint64_t>(bytes) + b0, a0 = addr & ~15ull;
-    // 32-bit positions within the span (len <= stage_bytes): byte w of
-    // vector v is span byte 16 v + w - lead, kept if below len (unsigned)
-    const uint32_t lead = (uint32_t)(addr - a0), len32 = (uint32_t)len;
-    const uint32_t nv = len32 ? (lead + len32 + 15) >> 4 : 0u;  // (an empty span: no vector holds a byte of it)
-    const V4 *src = reinterpret_cast<const V4 *>(a0);
-    for (uint32_t v0 = 0; v0 < nv; v0 += 4 * 256) {
-        V4 x[4];
-#pragma unroll
-        for (uint32_t u = 0; u < 4; ++u) {
-            const uint32_t v = v0 + u * 256 + threadIdx.x;
-            if (v < nv) x[u] = src[v];
-        }
-#pragma unroll
-        for (uint32_t u = 0; u < 4; ++u) {
-            const uint32_t v = v0 + u * 256 + threadIdx.x;
-            if (v >= nv) continue;
-            const uint32_t base = 16u * v - lead;
-#pragma unroll
-            for (uint32_t w = 0; w < 16; ++w) {
-                const uint32_t x0 = base + w;
-                if (x0 < len32)
-                    s_pat[rev ? len32 - 1u - x0 : x0] = s.enc[(x[u][w >> 2] >> (8 * (w & 3))) & 0xffu];
-            }
-        }
-    }
+    stage_span<kStrandNone>(s.enc, nullptr, s_pat, nullptr, bytes, b0, (uint32_t)len, rev);
     if (bad_stride) atomicOr(status, kStatusStride);
     return true;
 }
@@ -355,6 +370,7 @@ __device__ __forceinline__ void search_tile(const QueryArgs &a, const LocateGrou
     const uint32_t jb = group_batch(grp, vt);
     const LocateBatch &B = grp.b[jb];
     const uint32_t g = vt - grp.tile_begin[jb];
+    // (G spelled out, not tiles_of: with the call k_search's record store is scheduled differently, profiles/r13)
     const uint64_t G = (B.npat + 255) / 256, i = (uint64_t)g * 256u + threadIdx.x;
     SearchRec<P> *__restrict__ recs = reinterpret_cast<SearchRec<P> *>(B.tiles + 2 * G);
     P lo, rloc;
@@ -465,36 +481,7 @@ __device__ __forceinline__ PatView strand_pattern(const QueryArgs &a, const Tabl
     __syncthreads();
     staged = len <= stage_bytes / (both ? 2u : 1u);
     if (staged) {
-        using V4 = uint32_t __attribute__((ext_vector_type(4)));
-        // (stage_patterns' loop: vectors aligned by address, only those holding a byte of the span)
-        const uint64_t addr = reinterpret_cast<uint64_t>(bytes) + b0, a0 = addr & ~15ull;
-        const uint32_t lead = (uint32_t)(addr - a0), len32 = (uint32_t)len;
-        const uint32_t nv = len32 ? (lead + len32 + 15) >> 4 : 0u;
-        const V4 *src = reinterpret_cast<const V4 *>(a0);
-        uint8_t *s_fw = s_pat, *s_bw = s_pat + (both ? len32 : 0u);
-        for (uint32_t v0 = 0; v0 < nv; v0 += 4 * 256) {
-            V4 x[4];
-#pragma unroll
-            for (uint32_t u = 0; u < 4; ++u) {
-                const uint32_t q = v0 + u * 256 + threadIdx.x;
-                if (q < nv) x[u] = src[q];
-            }
-#pragma unroll
-            for (uint32_t u = 0; u < 4; ++u) {
-                const uint32_t q = v0 + u * 256 + threadIdx.x;
-                if (q >= nv) continue;
-                const uint32_t base = 16u * q - lead;
-#pragma unroll
-                for (uint32_t w = 0; w < 16; ++w) {
-                    const uint32_t x0 = base + w;
-                    if (x0 >= len32) continue;
-                    const uint32_t c = (x[u][w >> 2] >> (8 * (w & 3))) & 0xffu;
-                    const uint32_t at = rev ? len32 - 1u - x0 : x0;  // the span in pattern order
-                    if (both) s_fw[at] = s.enc[c];
-                    s_bw[len32 - 1u - at] = s_rc[c];
-                }
-            }
-        }
+        stage_span<ST>(s.enc, s_rc, s_pat, s_pat + (both ? (uint32_t)len : 0u), bytes, b0, (uint32_t)len, rev);
     }
     __syncthreads();
     PatView pv;
@@ -600,7 +587,7 @@ __global__ __launch_bounds__(256, 8) void k_match(const QueryArgs a, const Match
         rng[0] = lo;
         rng[1] = hi;
         if (loc) {
-            SearchRec<P> *__restrict__ recs = slot_records<P>(B.tiles, (npat + 255) / 256, 0);
+            SearchRec<P> *__restrict__ recs = slot_records<P>(B.tiles, tiles_of(npat), 0);
             const uint32_t need = B.min_len > 1u ? B.min_len : 1u;
             if (len >= need) cnt = slot_count<P>(lo, hi, B.max_occ);
             if (cnt == 1) recs[i] = make_record<P>(lo, cnt, true, locate_one<P, N, VB, REC>(a, s.C, lo, smp));
@@ -641,7 +628,7 @@ __global__ __launch_bounds__(256, 8) void k_seeds(const QueryArgs a, const SeedB
     }
     const uint32_t ms = B.max_seeds;
     const bool loc = B.tiles != nullptr;  // (workgroup-uniform)
-    const uint64_t G = (npat * ms + 255) / 256;  // the batch's 256-slot tiles
+    const uint64_t G = tiles_of(npat * ms);  // the batch's 256-slot tiles
     if (has) {
         // Per-lane state kept small (<u32,3,64,*> sit at the 64 VGPRs of 8 waves per SIMD): the prefix's end e
         // is the view's own m.
@@ -716,7 +703,7 @@ __global__ __launch_bounds__(256, 5) void k_approx(const QueryArgs a, const Appr
     }
     const uint32_t mh = B.max_hits;
     const bool loc = B.tiles != nullptr;         // (workgroup-uniform)
-    const uint64_t G = (npat * mh + 255) / 256;  // the batch's 256-slot tiles
+    const uint64_t G = tiles_of(npat * mh);  // the batch's 256-slot tiles
     if (has) {
         const uint64_t slot0 = first * mh;
         uint32_t *__restrict__ mm = B.out_mm + slot0;
@@ -887,7 +874,7 @@ __global__ __launch_bounds__(256, VAR == kVarDerivedLong ? 4 : 8) void k_locate(
     stage_tables(a, s, s_pat + stage_bytes);
     __syncthreads();
     const LocateBatch &B = grp.b[jb];
-    const uint64_t npat = B.npat, G = (npat + 255) / 256;
+    const uint64_t npat = B.npat, G = tiles_of(npat);
     const uint32_t g = claim_tile(grp, jb, G, &s_tk, a.status);
     if (g >= G) return;  // (workgroup-uniform)
     P lo, rloc;
@@ -920,7 +907,7 @@ using U4 = uint32_t __attribute__((ext_vector_type(4)));
 // id} per position), after its search records, 16-B aligned (24-B records
 // of u64 positions leave an odd count 8-B aligned).
 __device__ __forceinline__ U4 *group_sorted(const LocateBatch &B, uint32_t rec_bytes) {
-    const uint64_t n = B.npat, G = (n + 255) / 256;
+    const uint64_t n = B.npat, G = tiles_of(n);
     return reinterpret_cast<U4 *>(reinterpret_cast<uint8_t *>(B.tiles + 2 * G) + ((n * rec_bytes + 15) & ~15ull));
 }
 
@@ -1013,7 +1000,7 @@ __global__ __launch_bounds__(1024, W <= 8 ? 2 : 1) void k_group_key(const QueryA
     const uint32_t c = PLACE ? blockIdx.x : blockIdx.x * CPW + r;
     if constexpr (!PLACE) {
         const uint32_t nchunks = grp.chunk_begin[grp.n - 1] +
-                                 (uint32_t)(((grp.b[grp.n - 1].npat + 255) / 256 + kGroupChunkTiles - 1) /
+                                 (uint32_t)((tiles_of(grp.b[grp.n - 1].npat) + kGroupChunkTiles - 1) /
                                             kGroupChunkTiles);
         if (c >= nchunks) break;  // (workgroup-uniform)
     }
@@ -1438,7 +1425,7 @@ __global__ __launch_bounds__(256) void k_emit(const QueryArgs a, const LocateGro
     if (threadIdx.x <= a.sigma) sC[threadIdx.x] = (P)a.tab->C[threadIdx.x];
     const uint32_t jb = group_batch(grp, blockIdx.x);
     const LocateBatch &B = grp.b[jb];
-    const uint64_t npat = B.npat, G = (npat + 255) / 256;
+    const uint64_t npat = B.npat, G = tiles_of(npat);
     const uint64_t g0 = (uint64_t)(blockIdx.x - grp.tile_begin[jb]) * E;
     const SearchRec<P> *__restrict__ recs = reinterpret_cast<const SearchRec<P> *>(B.tiles + 2 * G);
     P lo[E], rloc[E];
@@ -1520,7 +1507,7 @@ __global__ __launch_bounds__(256) void k_emit_chain(const QueryArgs a, const Loc
     if (threadIdx.x <= a.sigma) sC[threadIdx.x] = (P)a.tab->C[threadIdx.x];
     __syncthreads();
     const LocateBatch &B = grp.b[jb];
-    const uint64_t npat = B.npat, G = (npat + 255) / 256;
+    const uint64_t npat = B.npat, G = tiles_of(npat);
     const uint32_t g = claim_tile(grp, jb, G, &s_tk, a.status);
     if (g >= G) return;  // (workgroup-uniform)
     const uint64_t i = (uint64_t)g * 256u + threadIdx.x;

@@ -54,23 +54,26 @@ hipError_t disp(uint32_t vb, uint32_t rec, F &&f) {
     return disp_rec<FMX_LAYOUT_VB>(rec, f);
 }
 
+// The search kernels: the instantiation of the search variant `var` (kVarFaithful / kVarDerived /
+// kVarDerivedLong); a record that exists in the faithful variant alone takes no other.  Inside a
+// disp() lambda: on that refusal it returns hipErrorInvalidValue from the lambda.
+#define FMX_LAUNCH_VARIANT(kernel, var, grid, lds, ...)                                                            \
+    do {                                                                                                            \
+        if ((var) == kVarFaithful)                                                                                  \
+            hipLaunchKernelGGL((kernel<P, N, VB, R, kVarFaithful>), dim3(grid), dim3(256), lds, s, __VA_ARGS__);    \
+        else if constexpr (faithful_only(R))                                                                        \
+            return hipErrorInvalidValue;                                                                            \
+        else if ((var) == kVarDerived)                                                                              \
+            hipLaunchKernelGGL((kernel<P, N, VB, R, kVarDerived>), dim3(grid), dim3(256), lds, s, __VA_ARGS__);     \
+        else                                                                                                        \
+            hipLaunchKernelGGL((kernel<P, N, VB, R, kVarDerivedLong>), dim3(grid), dim3(256), lds, s, __VA_ARGS__); \
+    } while (0)
+
 [[maybe_unused]] hipError_t op_count(const QueryArgs &qa, uint32_t vb, uint32_t rec, int var, const uint8_t *bytes,
                     const uint64_t *offs, uint64_t n, uint32_t flags, void *counts, uint32_t sb, hipStream_t s) {
     return disp(vb, rec, [&]<int VB, int R>() {
-        const uint32_t lds = sb + qa.kt_lds_bytes;
-        const dim3 g(grid_for(n)), b(256);
-        if (var == kVarFaithful) {
-            hipLaunchKernelGGL((k_count<P, N, VB, R, kVarFaithful>), g, b, lds, s, qa, bytes, offs, n, flags,
-                               (P *)counts, sb);
-        } else if constexpr (faithful_only(R)) {
-            return hipErrorInvalidValue;
-        } else if (var == kVarDerived) {
-            hipLaunchKernelGGL((k_count<P, N, VB, R, kVarDerived>), g, b, lds, s, qa, bytes, offs, n, flags,
-                               (P *)counts, sb);
-        } else {
-            hipLaunchKernelGGL((k_count<P, N, VB, R, kVarDerivedLong>), g, b, lds, s, qa, bytes, offs, n, flags,
-                               (P *)counts, sb);
-        }
+        FMX_LAUNCH_VARIANT(k_count, var, grid_for(n), sb + qa.kt_lds_bytes, qa, bytes, offs, n, flags, (P *)counts,
+                           sb);
         return hipGetLastError();
     });
 }
@@ -78,17 +81,7 @@ hipError_t disp(uint32_t vb, uint32_t rec, F &&f) {
 [[maybe_unused]] hipError_t op_search(const QueryArgs &qa, uint32_t vb, uint32_t rec, int var, const LocateGroup &grp,
                      uint32_t tiles, uint32_t sb, hipStream_t s) {
     return disp(vb, rec, [&]<int VB, int R>() {
-        const uint32_t lds = sb + qa.kt_lds_bytes;
-        if (var == kVarFaithful) {
-            hipLaunchKernelGGL((k_search<P, N, VB, R, kVarFaithful>), dim3(tiles), dim3(256), lds, s, qa, grp, sb);
-        } else if constexpr (faithful_only(R)) {
-            return hipErrorInvalidValue;
-        } else if (var == kVarDerived) {
-            hipLaunchKernelGGL((k_search<P, N, VB, R, kVarDerived>), dim3(tiles), dim3(256), lds, s, qa, grp, sb);
-        } else {
-            hipLaunchKernelGGL((k_search<P, N, VB, R, kVarDerivedLong>), dim3(tiles), dim3(256), lds, s, qa, grp,
-                               sb);
-        }
+        FMX_LAUNCH_VARIANT(k_search, var, tiles, sb + qa.kt_lds_bytes, qa, grp, sb);
         return hipGetLastError();
     });
 }
@@ -104,7 +97,7 @@ hipError_t disp(uint32_t vb, uint32_t rec, F &&f) {
 [[maybe_unused]] hipError_t op_search_grouped(const QueryArgs &qa, uint32_t vb, uint32_t rec, const LocateGroup &grp,
                                               uint64_t total, uint32_t cap, uint32_t opts, hipStream_t s) {
     return disp(vb, rec, [&]<int VB, int R>() {
-        const uint64_t grid = (total + 255) / 256;
+        const uint64_t grid = tiles_of(total);
         if (grid == 0 || grid > 0x7FFFFFFFull || cap == 0 || cap > kGroupRawStage) return hipErrorInvalidValue;
         hipLaunchKernelGGL((k_search_grouped<P, N, VB, R>), dim3((uint32_t)grid), dim3(256),
                            grouped_pat_bytes(cap, opts >> 8) + qa.kt_lds_bytes, s, qa, grp, total, cap, opts);
@@ -154,19 +147,7 @@ hipError_t disp(uint32_t vb, uint32_t rec, F &&f) {
 [[maybe_unused]] hipError_t op_locate(const QueryArgs &qa, uint32_t vb, uint32_t rec, int var, const LocateGroup &grp,
                                       uint32_t tiles, uint32_t sb, uint64_t tag, uint64_t late_ticks, hipStream_t s) {
     return disp(vb, rec, [&]<int VB, int R>() {
-        const uint32_t lds = sb + qa.kt_lds_bytes;
-        if (var == kVarFaithful) {
-            hipLaunchKernelGGL((k_locate<P, N, VB, R, kVarFaithful>), dim3(tiles), dim3(256), lds, s, qa, grp, sb, tag,
-                               late_ticks);
-        } else if constexpr (faithful_only(R)) {
-            return hipErrorInvalidValue;
-        } else if (var == kVarDerived) {
-            hipLaunchKernelGGL((k_locate<P, N, VB, R, kVarDerived>), dim3(tiles), dim3(256), lds, s, qa, grp, sb, tag,
-                               late_ticks);
-        } else {
-            hipLaunchKernelGGL((k_locate<P, N, VB, R, kVarDerivedLong>), dim3(tiles), dim3(256), lds, s, qa, grp, sb,
-                               tag, late_ticks);
-        }
+        FMX_LAUNCH_VARIANT(k_locate, var, tiles, sb + qa.kt_lds_bytes, qa, grp, sb, tag, late_ticks);
         return hipGetLastError();
     });
 }

@@ -38,16 +38,6 @@ void shard_of(uint64_t n, uint64_t parts, uint64_t p, uint64_t &s, uint64_t &e) 
     e = s + base + (p < extra ? 1 : 0);
 }
 
-struct CurrentDevice {  // restores the caller's current device
-    int prev = -1;
-    CurrentDevice() {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    }
-    ~CurrentDevice() {
-        if (prev >= 0) hipSetDevice(prev);
-    }
-};
-
 void free_multi(fmx_multi *m) {
     if (!m) return;
     for (fmx_index *x : m->ix) fmx_free(x);
@@ -80,16 +70,12 @@ fmx_status fmx_multi_load(const uint8_t *blob, uint64_t blob_len, fmx_layout lay
                           uint64_t *actual_total) {
     if (!out || !devices || n_devices <= 0 || n_devices > 64 || (!blob && blob_len)) return FMX_E_ARG;
     *out = nullptr;
-    BlobView bv;
-    BlobReader rd = [&](uint64_t off, uint64_t len, void *dst) {
-        if (off + len > blob_len) return false;
-        memcpy(dst, blob + off, len);
-        return true;
-    };
-    fmx_status st = parse_blob(rd, blob_len, layout, &bv, expected_total, actual_total);
+    // validated as fmx_load validates it
+    fmx_status st = load_index(host_reader(blob, blob_len), blob_len, layout, 0, 0, nullptr, nullptr, expected_total,
+                               actual_total);
     if (st) return st;
-    if (((uintptr_t)blob) % bv.align != 0) return FMX_E_ALIGN;
-    CurrentDevice keep;
+    if (((uintptr_t)blob) % align_of(layout) != 0) return FMX_E_ALIGN;
+    DeviceGuard keep;  // (restores the caller's current device)
     fmx_multi *m = new (std::nothrow) fmx_multi();
     if (!m) return FMX_E_DEVICE;
     m->devices.assign(devices, devices + n_devices);
@@ -131,7 +117,7 @@ fmx_status fmx_multi_load(const uint8_t *blob, uint64_t blob_len, fmx_layout lay
 }
 
 void fmx_multi_free(fmx_multi *m) {
-    CurrentDevice keep;
+    DeviceGuard keep;  // (restores the caller's current device)
     free_multi(m);
 }
 

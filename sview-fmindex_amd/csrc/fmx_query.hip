@@ -48,7 +48,7 @@ namespace fmx {
 __global__ __launch_bounds__(256) void k_scan(const LocateGroup grp) {
     __shared__ uint64_t s_scan[4];
     const LocateBatch &B = grp.b[blockIdx.x];
-    const uint64_t G = (B.npat + 255) / 256;
+    const uint64_t G = tiles_of(B.npat);
     const uint64_t *cnt = B.tiles;
     uint64_t *off = B.tiles + G;
     uint64_t carry = 0;
@@ -116,7 +116,7 @@ __global__ __launch_bounds__(256) void k_group_tiles(const LocateGroup grp) {
     __shared__ uint64_t s_w[E][4];
     const uint32_t jb = emit_batch(grp, blockIdx.x);
     const LocateBatch &B = grp.b[jb];
-    const uint64_t G = (B.npat + 255) / 256, g0 = (uint64_t)(blockIdx.x - grp.emit_begin[jb]) * E;
+    const uint64_t G = tiles_of(B.npat), g0 = (uint64_t)(blockIdx.x - grp.emit_begin[jb]) * E;
     const NarrowRec<P> *__restrict__ recs = reinterpret_cast<const NarrowRec<P> *>(B.tiles + 2 * G);
     uint64_t cnt[E];
 #pragma unroll
@@ -150,7 +150,7 @@ __global__ __launch_bounds__(256) void k_group_tiles(const LocateGroup grp) {
 // workgroup waits on another.
 
 __device__ __forceinline__ uint32_t *group_tally(const LocateBatch &B) {
-    return reinterpret_cast<uint32_t *>(B.tiles + 2 * ((B.npat + 255) / 256));
+    return reinterpret_cast<uint32_t *>(B.tiles + 2 * tiles_of(B.npat));
 }
 
 // 1. and 3.: every pattern's tally zeroed / checked to be 1 (one workgroup per tile)
@@ -331,7 +331,7 @@ static Disp dispatch(const fmx_index *ix) {
 
 
 // look-back tiles needed for n patterns (one per 256-pattern workgroup)
-uint64_t locate_tiles_cap(uint64_t n) { return (n + 255) / 256 > 0 ? (n + 255) / 256 : 1; }
+uint64_t locate_tiles_cap(uint64_t n) { return std::max<uint64_t>(tiles_of(n), 1); }
 
 static inline uint32_t stage_bytes_for(uint32_t flags) {
     const uint32_t kb = (flags >> 8) & 0xffu;  // FMX_HINT_STAGE_KB
@@ -348,11 +348,24 @@ static inline int search_var(const QueryArgs &qa, uint32_t sb) {
     return sb > (uint32_t)kStageBytes ? kVarDerivedLong : kVarDerived;
 }
 
+// The index's kernel arguments for a launch under the status word `status`.
+static QueryArgs args_for(const fmx_index *ix, uint32_t *status) {
+    QueryArgs qa = ix->qa;
+    qa.status = status;
+    return qa;
+}
+
+// f.template operator()<P>() for the index's position type.
+template <class F>
+static void by_pos(const fmx_index *ix, F &&f) {
+    if (ix->bv.L.pos_bytes == 4) f.template operator()<uint32_t>();
+    else f.template operator()<uint64_t>();
+}
+
 hipError_t launch_count(const fmx_index *ix, const uint8_t *d_bytes, const uint64_t *d_offsets, uint64_t n,
                         uint32_t flags, void *d_counts, uint32_t *status, hipStream_t stream) {
     if (n == 0) return hipSuccess;
-    QueryArgs qa = ix->qa;
-    qa.status = status;
+    const QueryArgs qa = args_for(ix, status);
     const Disp d = dispatch(ix);
     const uint32_t sb = stage_bytes_for(flags);
     return d.ops->count(qa, d.vb, d.rec, search_var(qa, sb), d_bytes, d_offsets, n, flags, d_counts, sb, stream);
@@ -401,7 +414,7 @@ static uint32_t group_pack_bits(const fmx_index *ix, const LocateGroup *grps, ui
 }
 
 static uint32_t group_tiles(const LocateGroup &grp) {
-    return grp.tile_begin[grp.n - 1] + (uint32_t)((grp.b[grp.n - 1].npat + 255) / 256);
+    return grp.tile_begin[grp.n - 1] + (uint32_t)tiles_of(grp.b[grp.n - 1].npat);
 }
 
 // k_group_tiles' workgroups of each batch (kEmitTiles tiles of one batch each); their count
@@ -409,7 +422,7 @@ static uint32_t set_emit_begin(LocateGroup &grp) {
     uint32_t ewg = 0;
     for (uint32_t j = 0; j < grp.n; ++j) {
         grp.emit_begin[j] = ewg;
-        ewg += (uint32_t)(((grp.b[j].npat + 255) / 256 + kEmitTiles - 1) / kEmitTiles);
+        ewg += (uint32_t)((tiles_of(grp.b[j].npat) + kEmitTiles - 1) / kEmitTiles);
     }
     return ewg;
 }
@@ -427,7 +440,7 @@ static hipError_t launch_emit(const fmx_index *ix, const QueryArgs &qa, const Lo
     // (a grouped launch's batches get k_scan: 885-895 vs 923-939 us per 102.4 M-pattern launch with
     // k_emit's own sums, profiles/r5/r5fold_*; FMX_EMIT_FOLD=1 / 0 forces either)
     uint32_t fold = (ix->emit_fold == 1 || (ix->emit_fold < 0 && !narrow)) ? 1u : 0u;
-    for (uint32_t j = 0; j < grp.n; ++j) fold &= (grp.b[j].npat + 255) / 256 <= kFoldTiles ? 1u : 0u;
+    for (uint32_t j = 0; j < grp.n; ++j) fold &= tiles_of(grp.b[j].npat) <= kFoldTiles ? 1u : 0u;
     if (!fold) {
         hipLaunchKernelGGL(k_scan, dim3(grp.n), dim3(256), 0, stream, grp);
         const hipError_t e = hipGetLastError();
@@ -471,7 +484,6 @@ static hipError_t launch_grouped(const fmx_index *ix, const QueryArgs &qa, Locat
                                  uint64_t total, uint32_t bits, bool raw, bool chain, hipStream_t stream,
                                  hipEvent_t mid) {
     const Disp d = dispatch(ix);
-    const bool p4 = ix->bv.L.pos_bytes == 4;
     const uint32_t rb = (uint32_t)locate_rec_bytes(ix->bv.L.pos_bytes);
     uint8_t *ws0 = reinterpret_cast<uint8_t *>(grps[0].b[0].tiles) - kWsHeader;
     uint32_t *gcount = reinterpret_cast<uint32_t *>(ws0 + 256);
@@ -487,7 +499,7 @@ static hipError_t launch_grouped(const fmx_index *ix, const QueryArgs &qa, Locat
         uint32_t chunks = 0;
         for (uint32_t j = 0; j < grp.n; ++j) {
             LocateBatch &B = grp.b[j];
-            const uint64_t G = (B.npat + 255) / 256;
+            const uint64_t G = tiles_of(B.npat);
             B.first = first;
             tab->first[gn] = first;
             tab->vfirst[gn] = (vt + grp.tile_begin[j]) * 256u;
@@ -566,7 +578,7 @@ static hipError_t launch_grouped(const fmx_index *ix, const QueryArgs &qa, Locat
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     if (ix->group_check) {
-        const uint32_t ord = (uint32_t)((total + 255) / 256);
+        const uint32_t ord = (uint32_t)tiles_of(total);
         for (uint32_t g = 0; g < ng; ++g)
             hipLaunchKernelGGL(k_group_check_tally<true>, dim3(group_tiles(grps[g])), dim3(256), 0, stream, qa,
                                grps[g]);
@@ -591,10 +603,9 @@ static hipError_t launch_grouped(const fmx_index *ix, const QueryArgs &qa, Locat
     if (!chain)
         for (uint32_t g = 0; g < ng; ++g) {
             const uint32_t ewg = set_emit_begin(grps[g]);
-            if (p4)
-                hipLaunchKernelGGL(k_group_tiles<uint32_t>, dim3(ewg), dim3(256), 0, stream, grps[g]);
-            else
-                hipLaunchKernelGGL(k_group_tiles<uint64_t>, dim3(ewg), dim3(256), 0, stream, grps[g]);
+            by_pos(ix, [&]<typename P>() {
+                hipLaunchKernelGGL(k_group_tiles<P>, dim3(ewg), dim3(256), 0, stream, grps[g]);
+            });
         }
     if ((e = hipGetLastError()) != hipSuccess) return e;
     (raw ? ix->launches_grouped_raw : ix->launches_grouped).fetch_add(1, std::memory_order_relaxed);
@@ -613,38 +624,45 @@ static hipError_t launch_grouped(const fmx_index *ix, const QueryArgs &qa, Locat
     return hipSuccess;
 }
 
-// Whether the ng groups (every batch with its fields filled, tile_begin[0] =
-// 0 in each) run as one grouped launch: the index has a key, every batch the
-// fixed-length hint, the launch at least grouped_min patterns (grouped_raw_min
-// when the records must be id-only), the faithful search, and 32-bit pattern
-// ids.
-static bool is_grouped(const fmx_index *ix, const QueryArgs &qa, const LocateGroup *grps, uint32_t ng, uint32_t sb,
-                       uint64_t *total, uint32_t *bits, bool *raw) {
-    uint64_t n = 0, tiles = 0;
+// How a locate launch over the ng groups (every batch with its fields filled,
+// tile_begin[0] = 0 in each) runs.  grouped: as one grouped launch — the index
+// has a key, every batch the fixed-length hint, the launch at least grouped_min
+// patterns (grouped_raw_min when the records must be id-only), the faithful
+// search, and 32-bit pattern ids; total, bits, raw: what launch_grouped takes
+// (group_pack_bits).  small: every batch has at most kFoldTiles tiles.  chain:
+// a grouped launch of small batches that k_emit_chain ends (FMX_EMIT_CHAIN=1),
+// unless the stream is being captured (a replayed graph would reuse the
+// launch's tag).
+struct LaunchPlan {
+    bool grouped, raw, small, chain;
+    uint64_t total;
+    uint32_t bits;
+};
+static LaunchPlan plan_launch(const fmx_index *ix, const QueryArgs &qa, const LocateGroup *grps, uint32_t ng,
+                              uint32_t sb, hipStream_t stream) {
+    LaunchPlan p{};
+    uint64_t tiles = 0;
+    p.small = true;
     for (uint32_t g = 0; g < ng; ++g) {
-        for (uint32_t j = 0; j < grps[g].n; ++j) n += grps[g].b[j].npat;
+        for (uint32_t j = 0; j < grps[g].n; ++j) {
+            p.total += grps[g].b[j].npat;
+            p.small = p.small && tiles_of(grps[g].b[j].npat) <= kFoldTiles;
+        }
         tiles += group_tiles(grps[g]);
     }
-    *total = n;
-    *bits = group_pack_bits(ix, grps, ng, raw);
-    return ix->gkey_len != 0 && *bits != 0 && n >= (*raw ? ix->grouped_raw_min : ix->grouped_min) &&
-           search_var(qa, sb) == kVarFaithful && tiles * 256u <= 0xFFFFFFFFull;
+    p.bits = group_pack_bits(ix, grps, ng, &p.raw);
+    p.grouped = ix->gkey_len != 0 && p.bits != 0 && p.total >= (p.raw ? ix->grouped_raw_min : ix->grouped_min) &&
+                search_var(qa, sb) == kVarFaithful && tiles * 256u <= 0xFFFFFFFFull;
+    p.chain = p.grouped && p.small && ix->emit_chain && !stream_capturing(stream);
+    return p;
 }
 
 // The kernels of a locate of one group, one after another on `stream`.
 static hipError_t launch_split(const fmx_index *ix, const QueryArgs &qa, LocateGroup &grp, uint32_t tiles,
                                uint32_t sb, hipStream_t stream, hipEvent_t mid = nullptr) {
     const Disp d = dispatch(ix);
-    uint64_t total = 0;
-    uint32_t bits = 0;
-    bool raw = false;
-    bool small = true;
-    for (uint32_t j = 0; small && j < grp.n; ++j) small = (grp.b[j].npat + 255) / 256 <= kFoldTiles;
-    if (is_grouped(ix, qa, &grp, 1, sb, &total, &bits, &raw)) {
-        // grouped, batches of at most kFoldTiles tiles: k_emit_chain may end the launch (FMX_EMIT_CHAIN=1)
-        const bool chain = small && ix->emit_chain && !stream_capturing(stream);
-        return launch_grouped(ix, qa, &grp, 1, total, bits, raw, chain, stream, mid);
-    }
+    const LaunchPlan p = plan_launch(ix, qa, &grp, 1, sb, stream);
+    if (p.grouped) return launch_grouped(ix, qa, &grp, 1, p.total, p.bits, p.raw, p.chain, stream, mid);
     uint64_t first = 0;
     for (uint32_t j = 0; j < grp.n; ++j) {
         grp.b[j].first = first;
@@ -652,7 +670,7 @@ static hipError_t launch_split(const fmx_index *ix, const QueryArgs &qa, LocateG
     }
     // in launch order, batches of at most kFoldTiles tiles of short fixed-length patterns: one kernel
     // (k_locate), unless the stream is being captured (a replayed graph would reuse the launch's tag)
-    bool fused = small && ix->fused && tiles <= ix->fused_max_tiles;
+    bool fused = p.small && ix->fused && tiles <= ix->fused_max_tiles;
     for (uint32_t j = 0; fused && j < grp.n; ++j) fused = grp.b[j].stride != 0 && grp.b[j].stride <= kFusedMaxLen;
     if (fused && stream_capturing(stream)) fused = false;
     hipError_t e;
@@ -677,16 +695,15 @@ hipError_t launch_locate(const fmx_index *ix, const uint8_t *d_bytes, const uint
                          uint64_t *d_needed, uint64_t *d_tiles, uint64_t tiles_cap, uint32_t *status,
                          hipStream_t stream) {
     if (n == 0) return hipSuccess;
-    QueryArgs qa = ix->qa;
-    qa.status = status;
-    if ((n + 255) / 256 > tiles_cap || tiles_cap > 0xFFFFFFFFull) return hipErrorInvalidValue;
+    const QueryArgs qa = args_for(ix, status);
+    if (tiles_of(n) > tiles_cap || tiles_cap > 0xFFFFFFFFull) return hipErrorInvalidValue;
     LocateGroup grp;
     group_reset(grp);
     grp.tile_begin[0] = 0;
     grp.b[0] = LocateBatch{d_bytes, d_offsets, n, d_counts, d_loc_offsets, d_locs, cap, d_needed, d_tiles,
                            flags_rev(flags), flags_stride(flags)};
     grp.n = 1;
-    return launch_split(ix, qa, grp, (uint32_t)((n + 255) / 256), stage_bytes_for(flags), stream);
+    return launch_split(ix, qa, grp, (uint32_t)tiles_of(n), stage_bytes_for(flags), stream);
 }
 
 // The slot queries (fmx_internal.hpp, LocOut): the query's own kernel, then —
@@ -707,7 +724,7 @@ static uint32_t slot_stage_bytes(uint32_t flags) {
 
 // Whether a launch takes `slots` slots: their 256-slot tiles, and with locations the workspace's room for them
 static bool slots_ok(uint64_t slots, const LocOut &out) {
-    const uint64_t tiles = (slots + 255) / 256;
+    const uint64_t tiles = tiles_of(slots);
     return tiles <= 0x7FFFFFFFull && (!out.loc_offsets || (tiles <= out.tiles_cap && out.tiles));
 }
 
@@ -720,7 +737,7 @@ static hipError_t emit_slots(const fmx_index *ix, const QueryArgs &qa, uint64_t 
     grp.b[0] = LocateBatch{nullptr, nullptr, slots, nullptr, out.loc_offsets, out.locs, out.cap, out.needed, out.tiles,
                            0u, 0u};
     grp.n = 1;
-    return launch_emit(ix, qa, grp, (uint32_t)((slots + 255) / 256), 0u, stream);
+    return launch_emit(ix, qa, grp, (uint32_t)tiles_of(slots), 0u, stream);
 }
 
 // Longest-suffix match: k_match, a slot per pattern.
@@ -728,59 +745,64 @@ hipError_t launch_match(const fmx_index *ix, const uint8_t *d_bytes, const uint6
                         uint32_t flags, uint32_t min_len, uint64_t max_occ, uint32_t *d_lens, void *d_ranges,
                         const LocOut &out, uint32_t *status, hipStream_t stream) {
     if (n == 0) return hipSuccess;
-    QueryArgs qa = ix->qa;
-    qa.status = status;
+    const QueryArgs qa = args_for(ix, status);
     if (!slots_ok(n, out)) return hipErrorInvalidValue;
     const bool loc = out.loc_offsets != nullptr;
     const MatchBatch mb{d_bytes, d_offsets, n, d_lens, d_ranges, loc ? out.tiles : nullptr, max_occ, min_len,
                         flags_rev(flags), flags_stride(flags)};
     const Disp d = dispatch(ix);
-    const hipError_t e = d.ops->match(qa, d.vb, d.rec, flags_strand(flags), mb, (uint32_t)((n + 255) / 256),
+    const hipError_t e = d.ops->match(qa, d.vb, d.rec, flags_strand(flags), mb, (uint32_t)tiles_of(n),
                                       slot_stage_bytes(flags), stream);
     return e != hipSuccess || !loc ? e : emit_slots(ix, qa, n, out, stream);
 }
 
-// Greedy seed chains: k_seeds (a workgroup per 256 patterns), max_seeds slots per pattern.
+// k_seeds and k_approx: a workgroup per 256 patterns, `per` slots (1..max_per) per pattern.  `op`: the
+// layout's launcher; batch(tiles): its batch struct, tiles null when no locations are asked for.
+template <class B>
+using SlotOp = hipError_t (*)(const QueryArgs &, uint32_t, uint32_t, int, const B &, uint32_t, uint32_t, hipStream_t);
+template <class B, class F>
+static hipError_t launch_slots(const fmx_index *ix, SlotOp<B> LayoutOps::*op, uint64_t n, uint32_t flags,
+                               uint32_t per, uint32_t max_per, const LocOut &out, uint32_t *status,
+                               hipStream_t stream, F &&batch) {
+    if (per == 0 || per > max_per || n > ~0ull / per) return hipErrorInvalidValue;
+    const QueryArgs qa = args_for(ix, status);
+    const uint64_t slots = n * per;
+    if (!slots_ok(slots, out)) return hipErrorInvalidValue;
+    const bool loc = out.loc_offsets != nullptr;
+    const B b = batch(loc ? out.tiles : nullptr);
+    const Disp d = dispatch(ix);
+    const hipError_t e = (d.ops->*op)(qa, d.vb, d.rec, flags_strand(flags), b, (uint32_t)tiles_of(n),
+                                      slot_stage_bytes(flags), stream);
+    return e != hipSuccess || !loc ? e : emit_slots(ix, qa, slots, out, stream);
+}
+
+// Greedy seed chains: k_seeds, max_seeds slots per pattern.
 hipError_t launch_seeds(const fmx_index *ix, const uint8_t *d_bytes, const uint64_t *d_offsets, uint64_t n,
                         uint32_t flags, uint32_t max_seeds, uint32_t min_len, uint32_t skip, uint64_t max_occ,
                         uint32_t *d_nseeds, uint32_t *d_rest, uint32_t *d_spans, void *d_ranges, const LocOut &out,
                         uint32_t *status, hipStream_t stream) {
     if (n == 0) return hipSuccess;
-    if (max_seeds == 0 || max_seeds > kMaxSeeds || n > ~0ull / max_seeds) return hipErrorInvalidValue;
-    QueryArgs qa = ix->qa;
-    qa.status = status;
-    const uint64_t slots = n * max_seeds, wgs = (n + 255) / 256;
-    if (!slots_ok(slots, out)) return hipErrorInvalidValue;
-    const bool loc = out.loc_offsets != nullptr;
-    const SeedBatch sb{d_bytes, d_offsets, n,        d_nseeds, d_rest,           d_spans,
-                       d_ranges, loc ? out.tiles : nullptr,    max_occ, max_seeds, min_len, skip,
-                       flags_rev(flags), flags_stride(flags)};
-    const Disp d = dispatch(ix);
-    const hipError_t e =
-        d.ops->seeds(qa, d.vb, d.rec, flags_strand(flags), sb, (uint32_t)wgs, slot_stage_bytes(flags), stream);
-    return e != hipSuccess || !loc ? e : emit_slots(ix, qa, slots, out, stream);
+    return launch_slots(ix, &LayoutOps::seeds, n, flags, max_seeds, kMaxSeeds, out, status, stream,
+                        [&](uint64_t *tiles) {
+        return SeedBatch{d_bytes, d_offsets, n,         d_nseeds, d_rest, d_spans,          d_ranges,
+                         tiles,   max_occ,   max_seeds, min_len,  skip,   flags_rev(flags), flags_stride(flags)};
+    });
 }
 
-// k-mismatch search: k_approx (a workgroup per 256 patterns), max_hits slots per pattern.
+// k-mismatch search: k_approx, max_hits slots per pattern.
 hipError_t launch_approx(const fmx_index *ix, const uint8_t *d_bytes, const uint64_t *d_offsets, uint64_t n,
                          uint32_t flags, uint32_t max_mm, uint32_t max_hits, uint32_t mode, uint64_t max_occ,
                          uint32_t *d_nhits, uint32_t *d_more, uint32_t *d_mm, uint32_t *d_subs, void *d_ranges,
                          const LocOut &out, uint32_t *status, hipStream_t stream) {
     if (n == 0) return hipSuccess;
-    if (max_mm > kMaxMismatch || max_hits == 0 || max_hits > kMaxHits || n > ~0ull / max_hits)
-        return hipErrorInvalidValue;
-    QueryArgs qa = ix->qa;
-    qa.status = status;
-    const uint64_t slots = n * max_hits, wgs = (n + 255) / 256;
-    if (!slots_ok(slots, out)) return hipErrorInvalidValue;
-    const bool loc = out.loc_offsets != nullptr;
-    const ApproxBatch ab{d_bytes, d_offsets, n,       d_nhits, d_more,   d_mm,
-                         d_subs,  d_ranges,  loc ? out.tiles : nullptr,  max_occ, max_mm, max_hits,
-                         (mode & FMX_APPROX_BEST) ? 1u : 0u, flags_rev(flags), flags_stride(flags)};
-    const Disp d = dispatch(ix);
-    const hipError_t e =
-        d.ops->approx(qa, d.vb, d.rec, flags_strand(flags), ab, (uint32_t)wgs, slot_stage_bytes(flags), stream);
-    return e != hipSuccess || !loc ? e : emit_slots(ix, qa, slots, out, stream);
+    if (max_mm > kMaxMismatch) return hipErrorInvalidValue;
+    return launch_slots(ix, &LayoutOps::approx, n, flags, max_hits, kMaxHits, out, status, stream,
+                        [&](uint64_t *tiles) {
+        return ApproxBatch{d_bytes, d_offsets, n,      d_nhits,  d_more,
+                           d_mm,    d_subs,    d_ranges, tiles,  max_occ,
+                           max_mm,  max_hits,  (mode & FMX_APPROX_BEST) ? 1u : 0u, flags_rev(flags),
+                           flags_stride(flags)};
+    });
 }
 
 static hipError_t check_group(const LocateGroup &grp, uint64_t *tiles) {
@@ -788,7 +810,7 @@ static hipError_t check_group(const LocateGroup &grp, uint64_t *tiles) {
     uint64_t t = 0;
     for (uint32_t j = 0; j < grp.n; ++j) {
         if (grp.b[j].npat == 0 || grp.tile_begin[j] != t) return hipErrorInvalidValue;
-        t += (grp.b[j].npat + 255) / 256;
+        t += tiles_of(grp.b[j].npat);
     }
     if (t > 0x7FFFFFFFull) return hipErrorInvalidValue;
     *tiles = t;
@@ -797,8 +819,7 @@ static hipError_t check_group(const LocateGroup &grp, uint64_t *tiles) {
 
 hipError_t launch_locate_group(const fmx_index *ix, LocateGroup &grp, uint32_t stage_flags,
                                uint32_t *status, hipStream_t stream, hipEvent_t mid) {
-    QueryArgs qa = ix->qa;
-    qa.status = status;
+    const QueryArgs qa = args_for(ix, status);
     uint64_t tiles = 0;
     hipError_t e = check_group(grp, &tiles);
     if (e != hipSuccess) return e;
@@ -809,23 +830,14 @@ hipError_t launch_locate_groups(const fmx_index *ix, LocateGroup *grps, uint32_t
                                 uint32_t *status, hipStream_t stream, hipEvent_t mid) {
     if (ng == 0 || (uint64_t)ng * kMaxGroup > kMaxMega) return hipErrorInvalidValue;
     if (ng == 1) return launch_locate_group(ix, grps[0], stage_flags, status, stream, mid);
-    QueryArgs qa = ix->qa;
-    qa.status = status;
+    const QueryArgs qa = args_for(ix, status);
     const uint32_t sb = stage_bytes_for(stage_flags);
     uint64_t tiles[kMaxMega / kMaxGroup];
     hipError_t e;
     for (uint32_t g = 0; g < ng; ++g)
         if ((e = check_group(grps[g], &tiles[g])) != hipSuccess) return e;
-    uint64_t total = 0;
-    uint32_t bits = 0;
-    bool raw = false;
-    if (is_grouped(ix, qa, grps, ng, sb, &total, &bits, &raw)) {
-        bool small = true;
-        for (uint32_t g = 0; g < ng; ++g)
-            for (uint32_t j = 0; small && j < grps[g].n; ++j) small = (grps[g].b[j].npat + 255) / 256 <= kFoldTiles;
-        const bool chain = small && ix->emit_chain && !stream_capturing(stream);
-        return launch_grouped(ix, qa, grps, ng, total, bits, raw, chain, stream, mid);
-    }
+    const LaunchPlan p = plan_launch(ix, qa, grps, ng, sb, stream);
+    if (p.grouped) return launch_grouped(ix, qa, grps, ng, p.total, p.bits, p.raw, p.chain, stream, mid);
     // in launch order: one launch per group (timing: the last group's search ends the first phase)
     for (uint32_t g = 0; g < ng; ++g)
         if ((e = launch_split(ix, qa, grps[g], (uint32_t)tiles[g], sb, stream, g + 1 == ng ? mid : nullptr)) !=
@@ -855,10 +867,9 @@ hipError_t build_deep_lut(fmx_index *ix, uint32_t K, hipStream_t stream) {
     auto buf = [&](uint32_t j) { return ((K - j) % 2 == 0) ? ix->d_dlut : tmp; };
     QueryArgs qa = ix->qa;
     qa.dlut = nullptr;
-    if (pb == 4)
-        hipLaunchKernelGGL((k_dlut_root<uint32_t>), dim3(1), dim3(64), 0, stream, qa, (uint32_t *)buf(1));
-    else
-        hipLaunchKernelGGL((k_dlut_root<uint64_t>), dim3(1), dim3(64), 0, stream, qa, (uint64_t *)buf(1));
+    by_pos(ix, [&]<typename P>() {
+        hipLaunchKernelGGL((k_dlut_root<P>), dim3(1), dim3(64), 0, stream, qa, (P *)buf(1));
+    });
     e = hipGetLastError();
     const Disp d = dispatch(ix);
     uint64_t np = sigma;
@@ -874,12 +885,10 @@ hipError_t build_deep_lut(fmx_index *ix, uint32_t K, hipStream_t stream) {
 
 hipError_t build_dlut_rows(fmx_index *ix, hipStream_t stream) {
     const uint64_t entries = ix->dlut_bytes / (2ull * ix->bv.L.pos_bytes);
-    if (ix->bv.L.pos_bytes == 4)
-        hipLaunchKernelGGL((k_dlut_rows<uint32_t>), dim3(grid_stride_for(entries)), dim3(256), 0, stream, ix->qa,
-                           entries, (uint32_t *)ix->d_dlut);
-    else
-        hipLaunchKernelGGL((k_dlut_rows<uint64_t>), dim3(grid_stride_for(entries)), dim3(256), 0, stream, ix->qa,
-                           entries, (uint64_t *)ix->d_dlut);
+    by_pos(ix, [&]<typename P>() {
+        hipLaunchKernelGGL((k_dlut_rows<P>), dim3(grid_stride_for(entries)), dim3(256), 0, stream, ix->qa, entries,
+                           (P *)ix->d_dlut);
+    });
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
     return e;
@@ -909,12 +918,10 @@ hipError_t build_text(fmx_index *ix, hipStream_t stream) {
     e = hipMemsetAsync(ix->d_text, 0, n + 16, stream);
     if (e != hipSuccess) return e;
     const uint32_t stride = ix->qa.sa_stride;
-    if (ix->bv.L.pos_bytes == 4)
-        hipLaunchKernelGGL((k_text<uint32_t>), dim3(grid_stride_for(n)), dim3(256), 0, stream, ix->qa, n,
-                           (const uint32_t *)ix->d_safull, stride, ix->d_text);
-    else
-        hipLaunchKernelGGL((k_text<uint64_t>), dim3(grid_stride_for(n)), dim3(256), 0, stream, ix->qa, n,
-                           (const uint64_t *)ix->d_safull, stride, ix->d_text);
+    by_pos(ix, [&]<typename P>() {
+        hipLaunchKernelGGL((k_text<P>), dim3(grid_stride_for(n)), dim3(256), 0, stream, ix->qa, n,
+                           (const P *)ix->d_safull, stride, ix->d_text);
+    });
     e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
     return e;
@@ -922,12 +929,10 @@ hipError_t build_text(fmx_index *ix, hipStream_t stream) {
 
 hipError_t build_row_context(fmx_index *ix, hipStream_t stream) {
     const uint64_t n = ix->bv.n;
-    if (ix->bv.L.pos_bytes == 4)
-        hipLaunchKernelGGL((k_row_ctx<uint32_t>), dim3(grid_stride_for(n)), dim3(256), 0, stream, ix->qa, n,
-                           ix->d_text, (uint32_t *)ix->d_safull);
-    else
-        hipLaunchKernelGGL((k_row_ctx<uint64_t>), dim3(grid_stride_for(n)), dim3(256), 0, stream, ix->qa, n,
-                           ix->d_text, (uint64_t *)ix->d_safull);
+    by_pos(ix, [&]<typename P>() {
+        hipLaunchKernelGGL((k_row_ctx<P>), dim3(grid_stride_for(n)), dim3(256), 0, stream, ix->qa, n, ix->d_text,
+                           (P *)ix->d_safull);
+    });
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
     return e;

@@ -78,3 +78,33 @@ def provenance_text(name):
         c1 = min(n, c0 + step)
         out[c0:c1] = lut[rng.integers(0, len(alphabet), c1 - c0, dtype=np.uint8)]
     return out
+
+
+def random_workspace_jobs(pkg, ix, orc, rng, text, sizes, length):
+    """The job list of a group launch (fmx_locate_group_async) whose buffers
+    start out full of random bytes: batch bi has sizes[bi] patterns of
+    length(bi) bytes drawn from `text` (every third batch reversed), its
+    offsets, locations, counts and workspace random, the oracle's answer in
+    "want".  Returns (the batches' buffers, their jobs)."""
+    bats, jobs = [], []
+    for bi, n in enumerate(sizes):
+        rev, m = bi % 3 == 2, length(bi)
+        starts = rng.integers(0, text.size - m, size=n)
+        pats = [text[s:s + m].tobytes() for s in starts]
+        data, offsets = pkg.pack_patterns(pats)
+        want = orc.locate_batch(data, offsets)
+        q = [p[::-1] for p in pats] if rev else pats
+        data, offsets = pkg.pack_patterns(q)
+        cap = int(want[1].size) + 8
+        ws = ix.locate_workspace_size(n)
+        b = dict(n=n, want=want, data=np.concatenate([data, np.zeros(16, np.uint8)]),
+                 off=offsets.view(np.int64).copy(), loff=rng.integers(0, 2**62, size=n + 1).astype(np.int64),
+                 locs=rng.integers(0, 2**31, size=cap).astype(np.int32), need=np.zeros(1, np.int64),
+                 cnt=rng.integers(0, 2**31, size=n).astype(np.int32),
+                 ws=rng.integers(0, 256, size=ws).astype(np.uint8))
+        jobs.append(ix.locate_job(b["data"].ctypes.data, b["off"].ctypes.data, n, b["loff"].ctypes.data,
+                                  b["locs"].ctypes.data, cap, b["need"].ctypes.data, b["ws"].ctypes.data, ws,
+                                  d_counts=b["cnt"].ctypes.data, reversed=rev, stage_kb=max(1, -(-256 * m // 1024)),
+                                  fixed_len=m))
+        bats.append(b)
+    return bats, jobs

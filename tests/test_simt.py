@@ -22,7 +22,7 @@ import os
 import numpy as np
 import pytest
 
-from _util import ALL_LAYOUTS, rand_chr_list, rand_pattern, rand_text, table_from_symbols
+from _util import ALL_LAYOUTS, rand_chr_list, rand_pattern, rand_text, random_workspace_jobs, table_from_symbols
 from _simt import simt_fixture
 
 
@@ -131,27 +131,7 @@ def test_group_launch_garbage_workspaces_simt(pkg, O, simt, monkeypatch):
     orc = O.OracleIndex(blob, O.layout(4, 3, 64, 0))
     ix = pkg.FmIndex.load(blob, pkg.u32, pkg.blocks.Block3(pkg.Vector.U64), options=1)
     sizes = [int(x) for x in np.random.default_rng(6).integers(1, 400, size=40)]
-    bats, jobs = [], []
-    for bi, n in enumerate(sizes):
-        rev, m = bi % 3 == 2, 1 + (bi * 7) % 32
-        starts = rng.integers(0, text.size - m, size=n)
-        pats = [text[s:s + m].tobytes() for s in starts]
-        data, offsets = pkg.pack_patterns(pats)
-        want = orc.locate_batch(data, offsets)
-        q = [p[::-1] for p in pats] if rev else pats
-        data, offsets = pkg.pack_patterns(q)
-        cap = int(want[1].size) + 8
-        ws = ix.locate_workspace_size(n)
-        b = dict(n=n, want=want, data=np.concatenate([data, np.zeros(16, np.uint8)]),
-                 off=offsets.view(np.int64).copy(), loff=rng.integers(0, 2**62, size=n + 1).astype(np.int64),
-                 locs=rng.integers(0, 2**31, size=cap).astype(np.int32), need=np.zeros(1, np.int64),
-                 cnt=rng.integers(0, 2**31, size=n).astype(np.int32),
-                 ws=rng.integers(0, 256, size=ws).astype(np.uint8))
-        jobs.append(ix.locate_job(b["data"].ctypes.data, b["off"].ctypes.data, n, b["loff"].ctypes.data,
-                                  b["locs"].ctypes.data, cap, b["need"].ctypes.data, b["ws"].ctypes.data, ws,
-                                  d_counts=b["cnt"].ctypes.data, reversed=rev, stage_kb=max(1, -(-256 * m // 1024)),
-                                  fixed_len=m))
-        bats.append(b)
+    bats, jobs = random_workspace_jobs(pkg, ix, orc, rng, text, sizes, lambda bi: 1 + (bi * 7) % 32)
     q = ix.job_queue(jobs)
     for rep in range(2):
         ix.locate_group_async(q)
@@ -525,27 +505,7 @@ def test_fused_group_garbage_workspaces_simt(pkg, O, fused, monkeypatch):
     orc = O.OracleIndex(blob, O.layout(4, 3, 64, 0))
     ix = pkg.FmIndex.load(blob, pkg.u32, pkg.blocks.Block3(pkg.Vector.U64), options=1)
     sizes = [int(x) for x in np.random.default_rng(7).integers(1, 1200, size=24)]
-    bats, jobs = [], []
-    for bi, n in enumerate(sizes):
-        rev, m = bi % 3 == 2, 2 + (bi * 5) % 22
-        starts = rng.integers(0, text.size - m, size=n)
-        pats = [text[s:s + m].tobytes() for s in starts]
-        data, offsets = pkg.pack_patterns(pats)
-        want = orc.locate_batch(data, offsets)
-        q = [p[::-1] for p in pats] if rev else pats
-        data, offsets = pkg.pack_patterns(q)
-        cap = int(want[1].size) + 8
-        ws = ix.locate_workspace_size(n)
-        b = dict(n=n, want=want, data=np.concatenate([data, np.zeros(16, np.uint8)]),
-                 off=offsets.view(np.int64).copy(), loff=rng.integers(0, 2**62, size=n + 1).astype(np.int64),
-                 locs=rng.integers(0, 2**31, size=cap).astype(np.int32), need=np.zeros(1, np.int64),
-                 cnt=rng.integers(0, 2**31, size=n).astype(np.int32),
-                 ws=rng.integers(0, 256, size=ws).astype(np.uint8))
-        jobs.append(ix.locate_job(b["data"].ctypes.data, b["off"].ctypes.data, n, b["loff"].ctypes.data,
-                                  b["locs"].ctypes.data, cap, b["need"].ctypes.data, b["ws"].ctypes.data, ws,
-                                  d_counts=b["cnt"].ctypes.data, reversed=rev, stage_kb=max(1, -(-256 * m // 1024)),
-                                  fixed_len=m))
-        bats.append(b)
+    bats, jobs = random_workspace_jobs(pkg, ix, orc, rng, text, sizes, lambda bi: 2 + (bi * 5) % 22)
     q = ix.job_queue(jobs)
     for rep in range(3):
         ix.locate_group_async(q)
@@ -618,27 +578,7 @@ def test_chained_grouped_emit_simt(pkg, O, fused, monkeypatch, seed):
     orc = O.OracleIndex(blob, O.layout(4, 3, 64, 0))
     ix = pkg.FmIndex.load(blob, pkg.u32, pkg.blocks.Block3(pkg.Vector.U64), options=1)
     sizes = [int(x) for x in np.random.default_rng(6 + seed).integers(1, 1500, size=40)]
-    bats, jobs = [], []
-    for bi, n in enumerate(sizes):
-        rev, m = bi % 3 == 2, 1 + (bi * 7) % 32
-        starts = rng.integers(0, text.size - m, size=n)
-        pats = [text[s:s + m].tobytes() for s in starts]
-        data, offsets = pkg.pack_patterns(pats)
-        want = orc.locate_batch(data, offsets)
-        q = [p[::-1] for p in pats] if rev else pats
-        data, offsets = pkg.pack_patterns(q)
-        cap = int(want[1].size) + 8
-        ws = ix.locate_workspace_size(n)
-        b = dict(n=n, want=want, data=np.concatenate([data, np.zeros(16, np.uint8)]),
-                 off=offsets.view(np.int64).copy(), loff=rng.integers(0, 2**62, size=n + 1).astype(np.int64),
-                 locs=rng.integers(0, 2**31, size=cap).astype(np.int32), need=np.zeros(1, np.int64),
-                 cnt=rng.integers(0, 2**31, size=n).astype(np.int32),
-                 ws=rng.integers(0, 256, size=ws).astype(np.uint8))
-        jobs.append(ix.locate_job(b["data"].ctypes.data, b["off"].ctypes.data, n, b["loff"].ctypes.data,
-                                  b["locs"].ctypes.data, cap, b["need"].ctypes.data, b["ws"].ctypes.data, ws,
-                                  d_counts=b["cnt"].ctypes.data, reversed=rev, stage_kb=max(1, -(-256 * m // 1024)),
-                                  fixed_len=m))
-        bats.append(b)
+    bats, jobs = random_workspace_jobs(pkg, ix, orc, rng, text, sizes, lambda bi: 1 + (bi * 7) % 32)
     q = ix.job_queue(jobs)
     for rep in range(2):
         ix.locate_group_async(q)
@@ -675,27 +615,7 @@ def test_launch_of_many_groups_simt(pkg, O, simt, monkeypatch, grouped):
     orc = O.OracleIndex(blob, O.layout(4, 3, 64, 0))
     ix = pkg.FmIndex.load(blob, pkg.u32, pkg.blocks.Block3(pkg.Vector.U64), options=1)
     sizes = [int(x) for x in np.random.default_rng(8).integers(1, 60, size=700)]
-    bats, jobs = [], []
-    for bi, n in enumerate(sizes):
-        rev, m = bi % 3 == 2, 2 + (bi * 11) % 28
-        starts = rng.integers(0, text.size - m, size=n)
-        pats = [text[s:s + m].tobytes() for s in starts]
-        data, offsets = pkg.pack_patterns(pats)
-        want = orc.locate_batch(data, offsets)
-        q = [p[::-1] for p in pats] if rev else pats
-        data, offsets = pkg.pack_patterns(q)
-        cap = int(want[1].size) + 8
-        ws = ix.locate_workspace_size(n)
-        b = dict(n=n, want=want, data=np.concatenate([data, np.zeros(16, np.uint8)]),
-                 off=offsets.view(np.int64).copy(), loff=rng.integers(0, 2**62, size=n + 1).astype(np.int64),
-                 locs=rng.integers(0, 2**31, size=cap).astype(np.int32), need=np.zeros(1, np.int64),
-                 cnt=rng.integers(0, 2**31, size=n).astype(np.int32),
-                 ws=rng.integers(0, 256, size=ws).astype(np.uint8))
-        jobs.append(ix.locate_job(b["data"].ctypes.data, b["off"].ctypes.data, n, b["loff"].ctypes.data,
-                                  b["locs"].ctypes.data, cap, b["need"].ctypes.data, b["ws"].ctypes.data, ws,
-                                  d_counts=b["cnt"].ctypes.data, reversed=rev, stage_kb=max(1, -(-256 * m // 1024)),
-                                  fixed_len=m))
-        bats.append(b)
+    bats, jobs = random_workspace_jobs(pkg, ix, orc, rng, text, sizes, lambda bi: 2 + (bi * 11) % 28)
     q = ix.job_queue(jobs)
     for rep in range(2):
         ix.locate_group_async(q)
