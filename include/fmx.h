@@ -566,6 +566,86 @@ fmx_status fmx_approx_batch_async(fmx_index *ix, const uint8_t *d_bytes, const u
                                   uint64_t *d_needed, void *d_workspace, uint64_t workspace_bytes,
                                   void *stream);
 
+/* ------------------------------------------------- placing reads: the vote
+ * What a read mapper does with a seed chain: every seed occurrence says where
+ * the READ would start in the text, occurrences that agree are grouped, and
+ * the few starts most of the read's seeds vote for are kept (no reference
+ * counterpart).  Added within ABI 8: FMX_ABI_VERSION is unchanged.
+ * fmx_vote_async reads exactly what a seeds launch with locations wrote for
+ * n_chains patterns at max_seeds slots each — d_nseeds, d_spans,
+ * d_loc_offsets, d_locs and the cap that launch was given; under
+ * FMX_BOTH_STRANDS the caller passes its 2n: a chain is a virtual pattern.
+ * Chain i owns slots s = i * max_seeds + j, j < nseeds[i]; seed j covers
+ * p[e-L..e) with e = spans[2s], L = spans[2s+1], and its locations are
+ * locs[loc_offsets[s] .. loc_offsets[s+1]), P-wide (none for a seed that did
+ * not report).
+ * HITS: the pairs (j, x), x a location of seed j, each with the DIAGONAL
+ * d = (int64)x - (int64)(e_j - L_j): where the read would start, negative when
+ * it would overhang the text's start.  H_i = loc_offsets[(i+1) max_seeds] -
+ * loc_offsets[i max_seeds].
+ * CLUSTERS: with the chain's hits sorted by (d, j), a new cluster starts at the
+ * first hit and wherever d[k] - d[k-1] > band (single linkage; band = 0: exact
+ * diagonals).  A cluster has pos = its smallest d, mask = the OR of 1u << j
+ * over its hits, and cover = the sum of L_j over the bits of mask: a seed with
+ * two hits in a cluster counts once, and as the seeds of a chain never overlap
+ * cover is the number of the read's symbols the cluster explains.  A cluster
+ * QUALIFIES when cover >= min_cover.
+ * OUTPUTS: the qualifying clusters by cover descending, then pos ascending
+ * (pos is unique per cluster: the order is total).  With Q of them, ncands[i]
+ * = min(Q, max_cands), flags[i] has FMX_VOTE_MORE iff Q > max_cands, and
+ * candidate k sits at c = i * max_cands + k: pos[c], cover[c], mask[c].  Every
+ * unused candidate slot is written as zeros: the outputs are fully defined.
+ * A chain with H_i > FMX_VOTE_MAX_HITS, or with loc_offsets[(i+1) max_seeds] >
+ * cap (its locations were not all written), gets ncands = 0, flags =
+ * FMX_VOTE_OVERFLOW and zeros; d_locs is never read at or past cap.  A chain
+ * with no hit: ncands = 0, flags = 0.
+ * Sizes and alignment: the rule of the device calls above — n_chains words for
+ * d_nseeds, d_ncands and d_flags, 2 n_chains max_seeds for d_spans, n_chains
+ * max_seeds + 1 offsets (8-B aligned), n_chains max_cands each for d_pos (8-B
+ * aligned), d_cover and d_mask (4), d_locs P-aligned; each accessed as
+ * elements of its own type only, exactly that size is enough.  No workspace,
+ * and nothing is latched in the status word.  n_chains = 0 is FMX_OK and
+ * launches nothing.  FMX_E_ARG: max_seeds outside 1..32, max_cands outside
+ * 1..16, a null pointer (d_locs may be null only when cap = 0), a misaligned
+ * pointer, more chains than a launch's 2^31 - 1 workgroups of four hold, an
+ * index whose text_len >= 2^58 (so that (d + 2^32) << 5 | j packs into one
+ * 64-bit sort key).
+ * One kernel, k_vote: a wavefront per chain, its up to 1,024 keys held 16 to a
+ * lane and sorted by a bitonic network (lanes exchange by shuffles, a lane's
+ * own keys in registers), clusters and their masks by segmented shuffle scans,
+ * the best max_cands by rounds of a wave arg-max; no LDS, no barrier.  Timer:
+ * "vote", one unit per chain. */
+#define FMX_VOTE_MAX_HITS 1024u   /* most seed occurrences one chain may bring to a vote */
+#define FMX_VOTE_OVERFLOW 1u      /* flags[i] bit: the chain had more (or reached past cap): no candidates */
+#define FMX_VOTE_MORE     2u      /* flags[i] bit: more than max_cands clusters qualified */
+fmx_status fmx_vote_async(fmx_index *ix, uint64_t n_chains, uint32_t max_seeds,
+                          const uint32_t *d_nseeds, const uint32_t *d_spans,
+                          const uint64_t *d_loc_offsets, const void *d_locs, uint64_t cap,
+                          uint32_t band, uint32_t min_cover, uint32_t max_cands,
+                          uint32_t *d_ncands, uint32_t *d_flags,
+                          int64_t *d_pos, uint32_t *d_cover, uint32_t *d_mask, void *stream);
+
+/* Host buffers, synchronous: seeds -> locations -> vote on the device.  The
+ * result is exactly fmx_vote_async applied to what fmx_seeds_batch returns
+ * for the same arguments with a large enough cap.  Strand flags are those of
+ * seeds: under FMX_BOTH_STRANDS every output is shaped for 2n chains, and a
+ * strand-1 candidate's pos is where rc(p) starts in the text.  Nothing but the
+ * reads goes up and nothing but the candidates comes down: seeds, locations
+ * and the workspace live in temporary HBM, bounded by running the batch in
+ * chunks of at most 65,536 reads (FMX_PLACE_CHUNK=<reads> in the environment
+ * at load overrides; the results are identical whatever the chunk).
+ * FMX_E_ARG when max_seeds * max_occ > FMX_VOTE_MAX_HITS (beside the argument
+ * checks of seeds and of the vote): no chain can then overflow, and the
+ * locations' capacity slots * max_occ is exact-or-over by construction, so
+ * there is no FMX_E_CAPACITY and no retry.  The call sets the staging and
+ * fixed-length hints itself, per chunk. */
+fmx_status fmx_place_batch(fmx_index *ix, const uint8_t *bytes, const uint64_t *offsets,
+                           uint64_t n_patterns, uint32_t flags,
+                           uint32_t max_seeds, uint32_t min_len, uint32_t skip, uint64_t max_occ,
+                           uint32_t band, uint32_t min_cover, uint32_t max_cands,
+                           uint32_t *out_ncands, uint32_t *out_flags,
+                           int64_t *out_pos, uint32_t *out_cover, uint32_t *out_mask);
+
 /* Wait for `stream` and return (and clear) the latched device status. */
 fmx_status fmx_sync(fmx_index *ix, void *stream);
 
@@ -614,7 +694,7 @@ fmx_status fmx_multi_locate_batch(fmx_multi *m, const uint8_t *bytes, const uint
  * several microseconds, so throughput runs sample (k > 1).  Timers: "count",
  * "locate" (a whole locate launch), "match" (a whole match launch), "seeds"
  * (a whole seed-chain launch, a unit per slot), "approx" (a whole k-mismatch
- * launch, a unit per slot) and, for
+ * launch, a unit per slot), "vote" (k_vote, a unit per chain) and, for
  * fmx_locate_group_async, its two kernels "locate.search" (k_search) and
  * "locate.emit" (k_emit). */
 fmx_status fmx_timing_enable(fmx_index *ix, int enable);

@@ -732,6 +732,49 @@ class FmIndex:
         return ((nh[:n], more[:n], mm[:n * mh].reshape(n, mh), subs[:n * mh].reshape(n, mh, 3, 2),
                  rng[:n * mh].reshape(n, mh, 2)) + ((loff, locs) if locate else ()))
 
+    # -- placing reads: seeds -> locations -> diagonal vote, all on the device --
+    def place(self, pattern: bytes, max_seeds: int = 8, min_len: int = 1, skip: int = 0, max_occ: int = 16,
+              band: int = 0, min_cover: int = 1, max_cands: int = 4, strands: str = "forward"):
+        """The read's candidate placements, best first: [(pos, cover, mask)] —
+        the read would start at text position pos (negative: it overhangs the
+        text's start), the seeds in `mask` (bit j: seed j of `seeds`) agree on
+        it and cover `cover` of its symbols.  strands="both": a (forward,
+        reverse) pair of such lists, the reverse one placing rc(pattern)."""
+        nc, _, pos, cover, mask = self.place_batch([pattern], max_seeds, min_len, skip, max_occ, band, min_cover,
+                                                   max_cands, strands=strands)
+        res = [[(int(pos[v, k]), int(cover[v, k]), int(mask[v, k])) for k in range(int(nc[v]))]
+               for v in range(nc.size)]
+        return tuple(res) if strands == "both" else res[0]
+
+    def place_batch(self, patterns, max_seeds: int = 8, min_len: int = 1, skip: int = 0, max_occ: int = 16,
+                    band: int = 0, min_cover: int = 1, max_cands: int = 4, reversed: bool = False,
+                    strands: str = "forward"):
+        """Candidate placements of many reads (fmx_place_batch): (ncands
+        uint32[n], flags uint32[n], pos int64[n, max_cands], cover uint32[n,
+        max_cands], mask uint32[n, max_cands]); 2n rows under strands="both".
+        The seeds of seeds_batch (max_seeds, min_len, skip; those with at most
+        max_occ occurrences are located; max_seeds * max_occ <= 1024) vote:
+        every occurrence x of seed j, covering p[e-L:e], says the read starts
+        at d = x - (e - L); occurrences whose d lie within `band` of their
+        neighbour's form a cluster with pos = its smallest d, mask = its seeds
+        and cover = their summed lengths; the clusters with cover >= min_cover
+        come by cover descending, then pos ascending, the first max_cands of
+        them stored (flags & 2: there were more) and the unused entries zero.
+        Only the reads go to the device and only the candidates come back."""
+        data, offsets = patterns if isinstance(patterns, tuple) else pack_patterns(patterns)
+        reads, K = offsets.size - 1, int(max_cands)
+        n = 2 * reads if strands == "both" else reads
+        rows = max(n, 1) * max(K, 1)
+        nc, fl = np.zeros(max(n, 1), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.uint32)
+        pos = np.zeros(rows, dtype=np.int64)
+        cover, mask = np.zeros(rows, dtype=np.uint32), np.zeros(rows, dtype=np.uint32)
+        flags = (_n.FMX_PATTERN_REVERSED if reversed else 0) | _strand_flags(strands)
+        _check(_n.lib().fmx_place_batch(self._h, _ptr(data) if data.size else None, _ptr(offsets), reads, flags,
+                                        int(max_seeds), int(min_len), int(skip), int(max_occ), int(band),
+                                        int(min_cover), K, _ptr(nc), _ptr(fl), _ptr(pos), _ptr(cover), _ptr(mask)),
+               "fmx_place_batch")
+        return (nc[:n], fl[:n], pos[:n * K].reshape(n, K), cover[:n * K].reshape(n, K), mask[:n * K].reshape(n, K))
+
     # -- device-resident API (pointers are ints; stream is a hipStream_t) --
     def count_batch_async(self, d_bytes: int, d_offsets: int, n: int, d_counts: int,
                           stream: int = 0, reversed: bool = False, long_patterns: bool = False, stage_kb: int = 0,
@@ -812,6 +855,22 @@ class FmIndex:
             _n.FMX_APPROX_BEST if best else 0, (1 << 64) - 1 if max_occ is None else int(max_occ), _vp(d_nhits),
             _vp(d_more), _vp(d_mm), _vp(d_subs), _vp(d_ranges), _vp(d_loc_offsets), _vp(d_locs), cap, _vp(d_needed),
             _vp(d_ws), ws_bytes, _vp(stream)))
+
+    def vote_async(self, n_chains: int, max_seeds: int, d_nseeds: int, d_spans: int, d_loc_offsets: int, d_locs: int,
+                   cap: int, d_ncands: int, d_flags: int, d_pos: int, d_cover: int, d_mask: int, band: int = 0,
+                   min_cover: int = 1, max_cands: int = 4, stream: int = 0) -> None:
+        """fmx_vote_async over what seeds_batch_async (with locations, `cap`
+        its capacity) left for n_chains patterns — 2n under strands="both" —
+        at max_seeds slots each: d_ncands, d_flags uint32[n_chains], d_pos
+        int64[n_chains max_cands], d_cover, d_mask uint32[n_chains max_cands]
+        (place_batch describes them).  A chain with more than 1,024
+        occurrences, or whose locations reach past cap: no candidates, flags =
+        1.  No workspace; on the same stream as the seeds launch no
+        synchronisation is needed in between."""
+        _check(_n.lib().fmx_vote_async(
+            self._h, n_chains, int(max_seeds), _vp(d_nseeds), _vp(d_spans), _vp(d_loc_offsets), _vp(d_locs), cap,
+            int(band), int(min_cover), int(max_cands), _vp(d_ncands), _vp(d_flags), _vp(d_pos), _vp(d_cover),
+            _vp(d_mask), _vp(stream)))
 
     @staticmethod
     def locate_job(d_bytes: int, d_offsets: int, n: int, d_loc_offsets: int, d_locs: int, cap: int,

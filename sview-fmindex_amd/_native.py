@@ -31,6 +31,9 @@ FMX_HINT_LONG_PATTERNS = 2
 FMX_PATTERN_REVCOMP = 4
 FMX_BOTH_STRANDS = 8
 FMX_APPROX_BEST = 1
+FMX_VOTE_MAX_HITS = 1024
+FMX_VOTE_OVERFLOW = 1
+FMX_VOTE_MORE = 2
 FMX_OCC_BLOB = 0
 FMX_OCC_INTERLEAVED = 1
 FMX_OPT_DEEP_LUT = 2
@@ -109,6 +112,8 @@ SIGNATURES = {
                               _PU64]),
     "fmx_approx_batch_async": (_i, [_p, _p, _p, _u64, _u32, _u32, _u32, _u32, _u64, _p, _p, _p, _p, _p, _p, _p, _u64, _p,
                                     _p, _u64, _p]),
+    "fmx_vote_async": (_i, [_p, _u64, _u32, _p, _p, _p, _p, _u64, _u32, _u32, _u32, _p, _p, _p, _p, _p, _p]),
+    "fmx_place_batch": (_i, [_p, _p, _p, _u64, _u32, _u32, _u32, _u32, _u64, _u32, _u32, _u32, _p, _p, _p, _p, _p]),
     "fmx_sync": (_i, [_p, _p]),
     "fmx_stream_release": (_i, [_p, _p]),
     "fmx_multi_load": (_i, [_p, _u64, fmx_layout, C.POINTER(_i), _i, _u32, C.POINTER(_p), _PU64, _PU64]),

@@ -535,6 +535,7 @@ hipError_t Stage::d2h(void *h, const void *d, uint64_t n, hipStream_t s) {
 //                                    25.6 M per launch it costs 462 us and saves 352)
 //   FMX_GROUP_REFINE     0           never refine (beats FMX_GROUP_REFINE_MIN)
 //   FMX_GROUP_CHECK      0 | 1 [0]   (debug) grouped launches check their sorted order (kStatusCheck)
+//   FMX_PLACE_CHUNK      n [65536]   fmx_place_batch answers its batch n reads at a time (>= 1; same results)
 static void read_policy_env(fmx_index *ix) {
     const char *e;
     if ((e = getenv("FMX_FUSED"))) ix->fused = e[0] != '0';
@@ -572,6 +573,8 @@ static void read_policy_env(fmx_index *ix) {
     if ((e = getenv("FMX_GROUP_REFINE_MIN"))) ix->group_refine_min = strtoull(e, nullptr, 10);
     if ((e = getenv("FMX_GROUP_REFINE")) && e[0] == '0') ix->group_refine_min = ~0ull;
     if ((e = getenv("FMX_GROUP_CHECK"))) ix->group_check = e[0] == '1';
+    ix->place_chunk = kPlaceChunk;
+    if ((e = getenv("FMX_PLACE_CHUNK"))) ix->place_chunk = std::max<uint64_t>(1, strtoull(e, nullptr, 10));
 }
 
 static fmx_status finish_load(fmx_index *ix, uint32_t options) {
@@ -1286,6 +1289,34 @@ fmx_status fmx_approx_batch_async(fmx_index *ix, const uint8_t *d_bytes, const u
                       });
 }
 
+// max_seeds and max_cands in range, and an index whose diagonals pack into k_vote's 64-bit sort key
+static bool vote_shape_ok(const fmx_index *ix, uint32_t max_seeds, uint32_t max_cands) {
+    return max_seeds >= 1 && max_seeds <= kMaxSeeds && max_cands >= 1 && max_cands <= kVoteMaxCands &&
+           ix->bv.n < (1ull << 58);
+}
+
+// The vote over a seeds launch's outputs.  Nothing is latched: no status word is taken.
+fmx_status fmx_vote_async(fmx_index *ix, uint64_t n, uint32_t max_seeds, const uint32_t *d_nseeds,
+                          const uint32_t *d_spans, const uint64_t *d_loc_offsets, const void *d_locs, uint64_t cap,
+                          uint32_t band, uint32_t min_cover, uint32_t max_cands, uint32_t *d_ncands, uint32_t *d_flags,
+                          int64_t *d_pos, uint32_t *d_cover, uint32_t *d_mask, void *stream) {
+    if (!ix || !vote_shape_ok(ix, max_seeds, max_cands) || n > 4 * 0x7FFFFFFFull) return FMX_E_ARG;
+    if (n == 0) return FMX_OK;
+    if (!d_nseeds || !d_spans || !d_loc_offsets || (cap && !d_locs) || !d_ncands || !d_flags || !d_pos || !d_cover ||
+        !d_mask)
+        return FMX_E_ARG;
+    const auto misaligned = [](const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; };
+    if (misaligned(d_nseeds, 4) || misaligned(d_spans, 4) || misaligned(d_loc_offsets, 8) ||
+        misaligned(d_locs, ix->bv.L.pos_bytes) || misaligned(d_ncands, 4) || misaligned(d_flags, 4) ||
+        misaligned(d_pos, 8) || misaligned(d_cover, 4) || misaligned(d_mask, 4))
+        return FMX_E_ARG;
+    hipStream_t s = stream ? (hipStream_t)stream : ix->stream;
+    DeviceGuard dg(ix->device);
+    const VoteBatch vb{n,   d_nseeds,  d_spans,  d_loc_offsets, d_locs, cap,   max_seeds, max_cands,
+                       band, min_cover, d_ncands, d_flags,       d_pos,  d_cover, d_mask};
+    return dev_err(timed(ix, "vote", s, n, [&](hipEvent_t) { return launch_vote(ix, vb, s); }));
+}
+
 fmx_status fmx_locate_jobs_async(fmx_index *ix, const fmx_locate_job *jobs, uint64_t n_jobs) {
     if (!ix || (n_jobs && !jobs)) return FMX_E_ARG;
     for (uint64_t i = 0; i < n_jobs; ++i) {
@@ -1647,6 +1678,56 @@ fmx_status fmx_approx_batch(fmx_index *ix, const uint8_t *bytes, const uint64_t 
                                                         loc ? (uint64_t *)(d + c.o_loff) : nullptr, d + c.o_locs, dcap,
                                                         (uint64_t *)(d + c.o_need), ix->d_ws, ix->ws_bytes, s);
                       });
+}
+
+// Placing reads: seeds, their locations and the vote on the device, a chunk of
+// at most ix->place_chunk reads at a time; of every chunk only its reads go up
+// and its candidates come down.  The seeds launch gets room for max_occ
+// locations per slot — no seed reports more —, so it cannot run short and no
+// chain's offsets reach past it; no retry.
+fmx_status fmx_place_batch(fmx_index *ix, const uint8_t *bytes, const uint64_t *offsets, uint64_t n, uint32_t flags,
+                           uint32_t max_seeds, uint32_t min_len, uint32_t skip, uint64_t max_occ, uint32_t band,
+                           uint32_t min_cover, uint32_t max_cands, uint32_t *out_ncands, uint32_t *out_flags,
+                           int64_t *out_pos, uint32_t *out_cover, uint32_t *out_mask) {
+    uint64_t nv;  // the virtual patterns: the outputs' shape
+    if (!ix || !strand_flags_ok(ix, flags) || !virtual_patterns(n, flags, &nv)) return FMX_E_ARG;
+    if (!vote_shape_ok(ix, max_seeds, max_cands) || !slots_shape_ok(nv, max_seeds, kMaxSeeds)) return FMX_E_ARG;
+    if (max_occ > kVoteMaxHits / max_seeds) return FMX_E_ARG;
+    if (n && (!offsets || !out_ncands || !out_flags || !out_pos || !out_cover || !out_mask)) return FMX_E_ARG;
+    if (n == 0) return FMX_OK;
+    if (!offsets_ok(bytes, offsets, n)) return FMX_E_ARG;
+    const uint64_t pb = ix->bv.L.pos_bytes, per = nv / n, K = max_cands;
+    std::vector<uint64_t> offs;  // a chunk's offsets, from zero
+    for (uint64_t a = 0; a < n; a += ix->place_chunk) {
+        const uint64_t nc = std::min(ix->place_chunk, n - a), cv = nc * per, v0 = a * per, slots = cv * max_seeds;
+        offs.resize(nc + 1);
+        for (uint64_t i = 0; i <= nc; ++i) offs[i] = offsets[a + i] - offsets[a];
+        Carve c(offs.data(), nc, flags);
+        const uint64_t o_nc = c.add(cv * 4, out_ncands + v0), o_fl = c.add(cv * 4, out_flags + v0);
+        const uint64_t o_pos = c.add(cv * K * 8, out_pos + v0 * K), o_cov = c.add(cv * K * 4, out_cover + v0 * K);
+        const uint64_t o_mask = c.add(cv * K * 4, out_mask + v0 * K);
+        // temporary: what the seeds launch writes and the vote reads
+        const uint64_t o_ns = c.add(cv * 4), o_rest = c.add(cv * 4), o_span = c.add(2 * slots * 4);
+        const uint64_t o_rng = c.add(2 * slots * pb), o_loff = c.add((slots + 1) * 8), o_need = c.add(8);
+        const uint64_t cap = slots * max_occ, o_locs = c.add(std::max<uint64_t>(cap, 1) * pb);
+        const fmx_status st = host_query(
+            ix, c, bytes ? bytes + offsets[a] : nullptr, offs.data(), nc, slots, false, nullptr, nullptr, 0, nullptr,
+            [&](uint8_t *d, uint64_t, hipStream_t s) {
+                fmx_status e = ensure_ws(ix, slots);  // (under ix->mu, as the scratch)
+                if (e) return e;
+                e = fmx_seeds_batch_async(ix, d, (uint64_t *)(d + c.o_off), nc, c.flags, max_seeds, min_len, skip,
+                                          max_occ, (uint32_t *)(d + o_ns), (uint32_t *)(d + o_rest),
+                                          (uint32_t *)(d + o_span), d + o_rng, (uint64_t *)(d + o_loff), d + o_locs,
+                                          cap, (uint64_t *)(d + o_need), ix->d_ws, ix->ws_bytes, s);
+                if (e) return e;
+                return fmx_vote_async(ix, cv, max_seeds, (uint32_t *)(d + o_ns), (uint32_t *)(d + o_span),
+                                      (uint64_t *)(d + o_loff), d + o_locs, cap, band, min_cover, max_cands,
+                                      (uint32_t *)(d + o_nc), (uint32_t *)(d + o_fl), (int64_t *)(d + o_pos),
+                                      (uint32_t *)(d + o_cov), (uint32_t *)(d + o_mask), s);
+            });
+        if (st) return st;
+    }
+    return FMX_OK;
 }
 
 // ---------------------------------------------------------------- timing

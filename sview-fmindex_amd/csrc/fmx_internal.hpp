@@ -276,6 +276,7 @@ struct fmx_index {
     bool fused_tickets = true;           // fused workgroups take their tile by ticket (d_tickets)
     bool emit_chain = false;             // grouped launches end with k_emit_chain
     int emit_fold = -1;                  // k_emit sums earlier tiles itself: 1 / 0 everywhere, -1 per path
+    uint64_t place_chunk = 0;            // reads per chunk of fmx_place_batch (set at load: kPlaceChunk)
     std::mutex status_mu;
     uint8_t *d_dlut = nullptr;
     uint64_t dlut_bytes = 0;
@@ -492,6 +493,29 @@ hipError_t launch_approx(const fmx_index *ix, const uint8_t *d_bytes, const uint
                          uint32_t flags, uint32_t max_mm, uint32_t max_hits, uint32_t mode, uint64_t max_occ,
                          uint32_t *d_nhits, uint32_t *d_more, uint32_t *d_mm, uint32_t *d_subs, void *d_ranges,
                          const LocOut &out, uint32_t *status, hipStream_t stream);
+// k_vote (fmx_vote_async): what a seeds launch with locations left for n chains of max_seeds slots, reduced per
+// chain to its best max_cands placements.  No index structure is read: the kernel depends on P alone.
+constexpr uint32_t kVoteMaxHits = FMX_VOTE_MAX_HITS;
+constexpr uint32_t kVoteMaxCands = 16;
+// fmx_place_batch answers its batch in chunks of this many reads (seeds, locations and workspace of one chunk
+// in temporary HBM: ~1 KB per read at max_seeds 8, max_occ 16 and u32 positions, at most ~10 KB);
+// FMX_PLACE_CHUNK at load overrides
+constexpr uint64_t kPlaceChunk = 1ull << 16;
+struct VoteBatch {
+    uint64_t n;
+    const uint32_t *nseeds;
+    const uint32_t *spans;  // 2 words per slot: end (exclusive), length
+    const uint64_t *loc_off;
+    const void *locs;  // P-wide
+    uint64_t cap;
+    uint32_t max_seeds, max_cands, band, min_cover;
+    uint32_t *out_ncands;
+    uint32_t *out_flags;
+    int64_t *out_pos;  // max_cands per chain, here and in the next two
+    uint32_t *out_cover;
+    uint32_t *out_mask;
+};
+hipError_t launch_vote(const fmx_index *ix, const VoteBatch &vb, hipStream_t stream);
 // `mid` (optional): an event recorded between k_search and k_emit (timing).
 // Fills grp's per-launch fields (first, emit_begin, the grouped fields) in place.
 hipError_t launch_locate_group(const fmx_index *ix, LocateGroup &grp, uint32_t stage_flags,

@@ -1582,4 +1582,83 @@ __global__ __launch_bounds__(256) void k_relayout(const QueryArgs a, uint64_t bl
                                 a.sigma);
 }
 
+// ------------------------------------------------------- k_vote's wave sort
+// (k_vote itself: fmx_query.hip.)  A wavefront holds the up to kVoteMaxHits
+// packed keys of one chain kVotePer to a lane — sorted position it * 64 + lane
+// is the lane's v[it] — and sorts the first 64 E of them (E a power of two,
+// wave-uniform) ascending with a bitonic network.  A step whose partner
+// distance is below 64 exchanges between lanes (__shfl_xor); from 64 on both
+// keys are the lane's own, in registers.  No LDS, so no barrier.
+constexpr uint32_t kVotePer = kVoteMaxHits / 64;
+constexpr uint64_t kVoteNone = ~0ull;  // no hit: sorts behind every key
+static_assert(kVotePer == 16, "vote_sort's in-lane steps are written for 16 keys per lane");
+// Between the unrolled steps of the network: the instruction scheduler may not move code across it.  Left
+// free it interleaves the 16 keys' exchanges for latency and holds all their temporaries at once — 248
+// VGPRs (2 waves per SIMD) against 88 (5) with the steps kept apart (the compiler's resource report).  No
+// instruction is emitted for it; the CPU emulation compiles it away.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define FMX_VOTE_ONE_AT_A_TIME() __builtin_amdgcn_sched_barrier(0)
+#else
+#define FMX_VOTE_ONE_AT_A_TIME() ((void)0)
+#endif
+
+// One in-lane step: partner distance 64 JJ, merge width k (>= 128, so the direction depends on `it` alone)
+template <uint32_t JJ>
+__device__ __forceinline__ void vote_step_regs(uint64_t (&v)[kVotePer], uint32_t E, uint32_t k) {
+#pragma unroll
+    for (uint32_t it = 0; it < kVotePer; ++it) {
+        if ((it & JJ) == 0 && it + JJ < E) {
+            const bool up = ((it << 6) & k) == 0;
+            const uint64_t a = v[it], b = v[it + JJ];
+            const uint64_t lo = a < b ? a : b, hi = a < b ? b : a;
+            v[it] = up ? lo : hi;
+            v[it + JJ] = up ? hi : lo;
+        }
+        FMX_VOTE_ONE_AT_A_TIME();
+    }
+}
+
+__device__ __forceinline__ void vote_sort(uint64_t (&v)[kVotePer], uint32_t E, uint32_t lane) {
+    const uint32_t N = 64 * E;
+    for (uint32_t k = 2; k <= N; k <<= 1) {
+        for (uint32_t j = k >> 1; j >= 64; j >>= 1) {
+            switch (j >> 6) {
+            case 1: vote_step_regs<1>(v, E, k); break;
+            case 2: vote_step_regs<2>(v, E, k); break;
+            case 4: vote_step_regs<4>(v, E, k); break;
+            default: vote_step_regs<8>(v, E, k); break;
+            }
+        }
+        for (uint32_t j = (k >> 1) < 32 ? (k >> 1) : 32; j >= 1; j >>= 1) {
+            // the lower lane of a pair keeps the smaller key where the merge ascends: by the lane's bit k below
+            // 64 keys, by the key's index `it` (wave-uniform) from there on
+            const bool low = (lane & j) == 0, lane_min = k < 64 ? ((lane & k) == 0) == low : low;
+#pragma unroll
+            for (uint32_t it = 0; it < kVotePer; ++it) {
+                if (it < E) {  // (wave-uniform: every lane takes part in the exchange)
+                    const uint64_t o = __shfl_xor(v[it], (int)j);
+                    const bool take_min = lane_min != ((it & (k >> 6)) != 0);
+                    v[it] = (o < v[it]) == take_min ? o : v[it];
+                }
+                FMX_VOTE_ONE_AT_A_TIME();
+            }
+        }
+    }
+}
+
+// v[r] for a run-time r < kVotePer.  Every key is read at its constant index and masked: a run-time index —
+// which is also what the compiler makes of a chain of selects between the keys — would move the array from
+// registers to scratch.
+__device__ __forceinline__ uint64_t vote_pick(const uint64_t (&v)[kVotePer], uint32_t r) {
+    uint64_t x = 0;
+#pragma unroll
+    for (uint32_t it = 0; it < kVotePer; ++it) x |= v[it] & (0 - (uint64_t)(r == it));
+    return x;
+}
+
+// Candidates in their output order: cover descending, then pos ascending
+__device__ __forceinline__ bool vote_better(uint32_t c1, int64_t p1, uint32_t c2, int64_t p2) {
+    return c1 > c2 || (c1 == c2 && p1 < p2);
+}
+
 }  // namespace fmx

@@ -138,6 +138,166 @@ __global__ __launch_bounds__(256) void k_group_tiles(const LocateGroup grp) {
                                     s_w[threadIdx.x][3];
 }
 
+// ------------------------------------------------------------------ k_vote
+// fmx_vote_async (include/fmx.h): a chain's seed occurrences -> the at most
+// max_cands read placements most of its seeds agree on.  A wavefront per
+// chain, 4 chains per workgroup; waves share nothing (no LDS, no barrier).
+//  1. lane t < max_seeds holds seed t: its first hit (relative to the chain's
+//     first), its start in the read e - L, and L; read by __shfl from here on.
+//  2. hit k of the chain (the chain's locations are one contiguous run of
+//     d_locs: coalesced loads) finds its seed by counting the seeds that start
+//     at or before k and becomes the key (d + 2^32) << 5 | j; kVoteNone pads.
+//  3. vote_sort (fmx_kernels.hpp).
+//  4. 64 sorted keys at a time: cluster heads where the diagonal jumps by more
+//     than band, a segmented scan (__shfl_up) that carries the head's diagonal
+//     and ORs the seed bits — its state at lane 63 carried into the next 64 —,
+//     cover at each cluster's last hit, and the qualifying clusters merged
+//     into the best max_cands so far (lane k holds candidate k) by rounds of a
+//     wave arg-max over (cover, pos).
+// Every wave operation is reached by the whole wave: the branches around them
+// depend on the chain alone.
+template <typename T>
+__device__ __forceinline__ T vote_wave_sum(T x) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) x += __shfl_xor(x, d);
+    return x;
+}
+
+template <typename P>
+__global__ __launch_bounds__(256) void k_vote(const VoteBatch B) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t c = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (c >= B.n) return;
+    const uint32_t ms = B.max_seeds, K = B.max_cands;
+    const uint64_t s0 = c * ms;
+    const uint64_t lo = B.loc_off[s0], hi = B.loc_off[s0 + ms], H = hi - lo;
+    const bool over = H > kVoteMaxHits || hi > B.cap;  // (hi < lo wraps H: overflow as well)
+    uint32_t E = 0;  // the chain's keys fill 64 E sorted positions (a power of two; 0: nothing to sort)
+    if (!over && H) {
+        E = 1;
+        while (64 * E < H) E <<= 1;
+    }
+    uint32_t Q = 0, b_cov = 0, b_mask = 0;
+    int64_t b_pos = 0;
+    bool b_has = false;
+    if (E) {
+        const uint32_t ns = B.nseeds[c] < ms ? B.nseeds[c] : ms;
+        uint32_t rel = ~0u, q = 0, L = 0;
+        if (lane < ms) {
+            const uint64_t o = B.loc_off[s0 + lane] - lo;
+            rel = o > H ? ~0u : (uint32_t)o;
+            if (lane < ns) {
+                L = B.spans[2 * (s0 + lane) + 1];
+                q = B.spans[2 * (s0 + lane)] - L;
+            }
+        }
+        const P *__restrict__ locs = reinterpret_cast<const P *>(B.locs);
+        uint64_t v[kVotePer];
+#pragma unroll
+        for (uint32_t it = 0; it < kVotePer; ++it) {
+            v[it] = kVoteNone;
+            if (it < E) {
+                const uint32_t k = it * 64 + lane;
+                uint32_t j = 0;
+                for (uint32_t t = 1; t < ms; ++t) j += __shfl(rel, (int)t) <= k ? 1u : 0u;
+                const uint32_t qj = __shfl(q, (int)j);
+                if (k < H && j < ns)
+                    v[it] = (((uint64_t)locs[lo + k] - qj + (1ull << 32)) << 5) | j;
+            }
+        }
+        vote_sort(v, E, lane);
+        uint32_t c_mask = 0;
+        int64_t c_pos = 0;
+        uint64_t last = kVoteNone;
+        for (uint32_t r = 0; r < E; ++r) {
+            const uint64_t key = vote_pick(v, r);
+            if (__shfl(key, 0) == kVoteNone) break;  // (sorted: nothing from here on)
+            const uint64_t after = __shfl(r + 1 < E ? vote_pick(v, r + 1) : kVoteNone, 0);
+            uint64_t pk = __shfl_up(key, 1), nk = __shfl(key, (int)((lane + 1) & 63));
+            if (lane == 0) pk = last;
+            if (lane == 63) nk = after;
+            const bool valid = key != kVoteNone;
+            const bool head = valid && ((r == 0 && lane == 0) || (key >> 5) - (pk >> 5) > B.band);
+            const bool tail = valid && (nk == kVoteNone || (nk >> 5) - (key >> 5) > B.band);
+            uint32_t m = valid ? 1u << (key & 31) : 0u, f = head ? 1u : 0u;
+            int64_t p = (int64_t)(key >> 5) - (1ll << 32);
+#pragma unroll
+            for (uint32_t d = 1; d < 64; d <<= 1) {
+                const uint32_t tm = __shfl_up(m, d), tf = __shfl_up(f, d);
+                const int64_t tp = __shfl_up(p, d);
+                if (lane >= d) {
+                    if (!f) {
+                        m |= tm;
+                        p = tp;
+                    }
+                    f |= tf;
+                }
+            }
+            if (!f) {  // the cluster began in an earlier 64
+                m |= c_mask;
+                p = c_pos;
+            }
+            c_mask = __shfl(m, 63);
+            c_pos = __shfl(p, 63);
+            last = __shfl(key, 63);
+            uint32_t cov = 0;
+            for (uint32_t t = 0; t < ms; ++t) {
+                const uint32_t Lt = __shfl(L, (int)t);
+                cov += ((m >> t) & 1u) ? Lt : 0u;
+            }
+            bool a_live = tail && cov >= B.min_cover;
+            const uint32_t fresh = vote_wave_sum(a_live ? 1u : 0u);
+            if (!fresh) continue;
+            Q += fresh;
+            // the best K of (the best so far, this 64's qualifying clusters): pos is unique per cluster
+            bool b_live = b_has;
+            uint32_t n_cov = 0, n_mask = 0;
+            int64_t n_pos = 0;
+            bool n_has = false;
+            for (uint32_t k = 0; k < K; ++k) {
+                const bool mine = a_live && (!b_live || vote_better(cov, p, b_cov, b_pos));
+                uint32_t w_any = (a_live || b_live) ? 1u : 0u, w_cov = mine ? cov : b_cov, w_mask = mine ? m : b_mask;
+                int64_t w_pos = mine ? p : b_pos;
+#pragma unroll
+                for (int d = 32; d > 0; d >>= 1) {
+                    const uint32_t o_any = __shfl_xor(w_any, d), o_cov = __shfl_xor(w_cov, d),
+                                   o_mask = __shfl_xor(w_mask, d);
+                    const int64_t o_pos = __shfl_xor(w_pos, d);
+                    if (o_any && (!w_any || vote_better(o_cov, o_pos, w_cov, w_pos))) {
+                        w_any = 1u;
+                        w_cov = o_cov;
+                        w_mask = o_mask;
+                        w_pos = o_pos;
+                    }
+                }
+                if (!w_any) break;  // (the same in every lane)
+                if (a_live && p == w_pos) a_live = false;
+                if (b_live && b_pos == w_pos) b_live = false;
+                if (lane == k) {
+                    n_cov = w_cov;
+                    n_mask = w_mask;
+                    n_pos = w_pos;
+                    n_has = true;
+                }
+            }
+            b_cov = n_cov;
+            b_mask = n_mask;
+            b_pos = n_pos;
+            b_has = n_has;
+        }
+    }
+    if (lane == 0) {
+        B.out_ncands[c] = Q < K ? Q : K;
+        B.out_flags[c] = over ? FMX_VOTE_OVERFLOW : Q > K ? FMX_VOTE_MORE : 0u;
+    }
+    if (lane < K) {
+        const uint64_t o = c * K + lane;
+        B.out_pos[o] = b_has ? b_pos : 0;
+        B.out_cover[o] = b_has ? b_cov : 0u;
+        B.out_mask[o] = b_has ? b_mask : 0u;
+    }
+}
+
 // ------------------------------------------- grouped launches: debug check
 // FMX_GROUP_CHECK=1 (fmx_index::group_check): after the place (and refine)
 // pass and before the search, the launch's sorted order is checked against
@@ -803,6 +963,17 @@ hipError_t launch_approx(const fmx_index *ix, const uint8_t *d_bytes, const uint
                            max_mm,  max_hits,  (mode & FMX_APPROX_BEST) ? 1u : 0u, flags_rev(flags),
                            flags_stride(flags)};
     });
+}
+
+// The vote over a seeds launch's outputs: k_vote, 4 chains per workgroup.
+hipError_t launch_vote(const fmx_index *ix, const VoteBatch &vb, hipStream_t stream) {
+    if (vb.n == 0) return hipSuccess;
+    const uint64_t wgs = (vb.n + 3) / 4;
+    if (wgs > 0x7FFFFFFFull || vb.max_seeds == 0 || vb.max_seeds > kMaxSeeds || vb.max_cands == 0 ||
+        vb.max_cands > kVoteMaxCands)
+        return hipErrorInvalidValue;
+    by_pos(ix, [&]<typename P>() { hipLaunchKernelGGL(k_vote<P>, dim3((uint32_t)wgs), dim3(256), 0, stream, vb); });
+    return hipGetLastError();
 }
 
 static hipError_t check_group(const LocateGroup &grp, uint64_t *tiles) {
