@@ -1,6 +1,7 @@
-"""Greedy seed chains (fmx_seeds_batch): the cases and expected values the
-emulator tests (test_seeds_simt.py) and the GPU tests (test_gpu_seeds.py)
-share.
+"""Greedy seed chains (fmx_seeds_batch): the cases, their bodies and the
+expected values the emulator tests (test_seeds_simt.py) and the GPU tests
+(test_gpu_seeds.py) share.  A body takes what differs between the two: the
+batch size, the layouts to visit, the device memory (_util.HostDev / TorchDev).
 
 The reference is built only from _match_cases.Case.expected, which already
 ties the oracle to a plainly sorted suffix list: Python runs the loop of
@@ -22,37 +23,16 @@ so that the batches of 255,
 wrong, hold every class as well (assert_classes below, on the expected values
 alone).
 """
-import numpy as np
+import ctypes as C
 
-from _match_cases import ABSENT, Case
+import numpy as np
+import pytest
+
+from _match_cases import ABSENT
+from _util import block_of, case_for, open_index, pos_of  # noqa: F401
 
 BATCH_SIZES = (1, 255, 256, 257, 700)
-_CASES = {}
 _POOLS = {}
-
-
-def case_for(planes, two_letters=False, **kw):
-    """One text per alphabet size (its expected values are computed once and
-    shared by every test of the run)."""
-    key = (planes, two_letters, tuple(sorted(kw.items())))
-    if key not in _CASES:
-        nchars = 2 if two_letters else min((1 << planes) - 1, 20)
-        _CASES[key] = Case(planes * 11 + (5 if two_letters else 0), nchars, **kw)
-    return _CASES[key]
-
-
-def pos_of(pkg, pb):
-    return pkg.u32 if pb == 4 else pkg.u64
-
-
-def block_of(pkg, planes, vb):
-    return getattr(pkg.blocks, f"Block{planes}")(pkg.Vector(vb))
-
-
-def open_index(pkg, O, case, pb, planes, vb, occ):
-    blob = case.blob(O, pb, planes, vb)
-    orc = O.OracleIndex(blob, O.layout(pb, planes, vb, 0))
-    return pkg.FmIndex.load(blob, pos_of(pkg, pb), block_of(pkg, planes, vb), options=occ), orc
 
 
 def _pool(case):
@@ -177,3 +157,159 @@ def cross_check(ix, pats, got):
         a, b = int(loff[i * ms]), int(loff[i * ms + 1])
         assert np.array_equal(locs[a:b], wlocs[int(woff[j]):int(woff[j + 1])])
         assert int(loff[i * ms + ms]) == b  # (its other slots hold nothing)
+
+
+# ------------------------------------------------------------------ the cases
+
+def two_letters(pkg, O, n, sr, layouts):
+    """A two-letter text: seeds with hundreds of rows (the row dealing of
+    k_emit), under every sampling ratio's walk."""
+    case = case_for(2, two_letters=True, k=3, sr=sr)
+    for pb, vb in layouts:
+        ix, orc = open_index(pkg, O, case, pb, 2, vb, 1)
+        pats = batch(case, n)
+        exp, _ = check_seeds(ix, orc, case, pats, max_seeds=3, skip=1)
+        assert int(np.diff(exp[4]).max()) >= 300
+        check_seeds(ix, orc, case, pats, max_seeds=3, reversed=True, max_occ=400)
+        ix.close()
+
+
+def filters(pkg, O, n, min_len):
+    """min_len decides what is a seed; max_occ only which seeds are located:
+    spans and ranges are the same across max_occ."""
+    case = case_for(3, k=3, sr=2)
+    ix, orc = open_index(pkg, O, case, 4, 3, 64, 1)
+    pats = batch(case, n)
+    first = None
+    for max_occ in (0, 1, 10, None):
+        exp, got = check_seeds(ix, orc, case, pats, max_seeds=3, min_len=min_len, skip=1, max_occ=max_occ)
+        first = first or got
+        assert np.array_equal(got[2], first[2]) and np.array_equal(got[3], first[3])
+        if max_occ == 0:
+            assert got[5].size == 0
+    if min_len == 5:
+        assert (exp[0] == 0).sum() >= 30 and (exp[2][:, :, 1][exp[2][:, :, 1] > 0] >= 5).all()
+    ix.close()
+
+
+def ranges_only_and_capacity(pkg, O, n):
+    case = case_for(3, k=3, sr=2)
+    ix, orc = open_index(pkg, O, case, 4, 3, 64, 1)
+    pats = batch(case, n)
+    check_seeds(ix, orc, case, pats, max_seeds=3, skip=1, locate=False)
+    s, rest = chain(case, orc, pats[5], 8, 1, 0)
+    assert ix.seeds(pats[5]) == [x[:4] for x in s] and rest == 0
+    assert ix.seeds(b"") == [] and ix.seeds(bytes([ABSENT])) == []
+    many = bytes([ABSENT, case.chars[0]]) * 20
+    assert many in pats and len(ix.seeds(many, max_seeds=32)) == 20
+    # a cap below needed: FMX_E_CAPACITY, needed exact, everything but the locations written
+    ms = 3
+    exp = expected_arrays(case, orc, pats, ms, 1, 0, None)
+    total = int(exp[4][-1])
+    data, offsets = pkg.pack_patterns(pats)
+    lib, nat = pkg._native.lib(), pkg._native
+
+    def call(cap, ns_ptr=True, max_seeds=ms):
+        o = [np.full(n, 7, np.uint32), np.full(n, 7, np.uint32), np.full((n, ms, 2), 7, np.uint32),
+             np.full((n, ms, 2), 7, np.uint32), np.full(n * ms + 1, 7, np.uint64), np.full(max(total, 1), 7, np.uint32)]
+        needed = C.c_uint64(99)
+        st = lib.fmx_seeds_batch(ix.handle, data.ctypes.data, offsets.ctypes.data, n, 0, max_seeds, 1, 0, (1 << 64) - 1,
+                                 o[0].ctypes.data if ns_ptr else None, o[1].ctypes.data, o[2].ctypes.data,
+                                 o[3].ctypes.data, o[4].ctypes.data, o[5].ctypes.data, cap, C.byref(needed))
+        return st, needed.value, o
+    st, needed, o = call(total - 1)
+    assert st == nat.FMX_E_CAPACITY and needed == total
+    compare(o[:4], exp, locate=False)
+    assert np.array_equal(o[4], exp[4])
+    st, needed, o = call(total)
+    assert st == 0 and needed == total
+    compare(o[:5] + [o[5][:total]], exp)
+    # argument checks
+    assert call(total, max_seeds=0)[0] == nat.FMX_E_ARG and call(total, max_seeds=33)[0] == nat.FMX_E_ARG
+    assert call(total, ns_ptr=False)[0] == nat.FMX_E_ARG
+    ix.close()
+
+
+def pass_through(pkg, O):
+    """PassThrough: bytes >= symbol_count in mid-pattern split it into seeds
+    on both sides (no FMX_E_SYMBOL, nothing latched)."""
+    rng = np.random.default_rng(13)
+    sigma, k = 5, 3
+    text = bytes(rng.integers(0, 4, size=1500).astype(np.uint8))  # symbols 0..3; 4 never occurs
+    blob = O.build(text, sigma, O.layout(4, 3, 64), k, 2, None)
+    orc = O.OracleIndex(blob, O.layout(4, 3, 64, 1))
+    ix = pkg.FmIndex.load(blob, pkg.u32, pkg.blocks.Block3(pkg.Vector.U64), pkg.text_encoders.PassThrough, options=1)
+    pats, parts = [], []
+    for la, lb in [(1, 1), (2, 3), (3, 2), (9, 4), (4, 9), (12, 12)] * 6:
+        a0, b0 = int(rng.integers(0, len(text) - la)), int(rng.integers(0, len(text) - lb))
+        a, b = text[a0:a0 + la], text[b0:b0 + lb]
+        for bad in (bytes([9]), bytes([200]), bytes([4, 77])):
+            pats.append(a + bad + b)
+            parts.append((a, bad, b))
+    for skip in (0, 1):
+        ns, rest, spans, rg, loff, locs = ix.seeds_batch(pats, max_seeds=4, skip=skip)
+        for i, (a, bad, b) in enumerate(parts):
+            m = len(pats[i])
+            assert ns[i] == 2 and rest[i] == 0, (i, pats[i])
+            assert spans[i, :2].tolist() == [[m, len(b)], [len(a), len(a)]] and spans[i, 2:].tolist() == [[0, 0]] * 2
+            for j, sub in enumerate((b, a)):
+                assert int(rg[i, j, 1] - rg[i, j, 0]) == orc.count(sub)
+                assert locs[int(loff[4 * i + j]):int(loff[4 * i + j + 1])].tolist() == orc.locate(sub)
+    ix.sync()  # nothing latched
+    ix.close()
+
+
+def device_call(pkg, O, dev, n):
+    """fmx_seeds_batch_async over buffers in `dev`: with locations over a
+    garbage workspace and prefilled outputs, ranges only with no workspace, a
+    disagreeing FMX_HINT_FIXED_LEN still FMX_E_ARG, the "seeds" timer, the
+    argument checks."""
+    case = case_for(3, k=3, sr=2)
+    ix, orc = open_index(pkg, O, case, 4, 3, 64, 1)
+    pats = batch(case, n)
+    ms = 3
+    exp = expected_arrays(case, orc, pats, ms, 5, 1, 10)
+    total = int(exp[4][-1])
+    ins = [dev.put(a) for a in pkg.pack_patterns(pats)]
+    d_data, d_off = ins[0][1], ins[1][1]
+    rnd = np.random.default_rng(4)
+    shapes = [(n,), (n,), (n, ms, 2), (n, ms, 2), (n * ms + 1,), (total + 4,)]
+    dts = [np.uint32] * 4 + [np.uint64, np.uint32]
+    o = [dev.filled(rnd, sh, dt) for sh, dt in zip(shapes, dts)]
+    need = dev.filled(rnd, 1, np.uint64)
+    wsb = ix.locate_workspace_size(n * ms)
+    ws = dev.workspace(rnd, wsb)
+    dev.sync()
+    ix.timing_enable(True)
+    ix.seeds_batch_async(d_data, d_off, n, *[x[1] for x in o], total + 4, need[1], ws[1], wsb, max_seeds=ms, min_len=5,
+                         skip=1, max_occ=10)
+    ix.sync()
+    assert ix.timing_read()["seeds"]["launches"] == 1
+    ix.timing_enable(False)
+    assert int(dev.get(need[0], np.uint64)[0]) == total
+    got = [dev.get(x[0], dt).reshape(sh) for x, sh, dt in zip(o, shapes, dts)]
+    compare(got[:5] + [got[5][:total]], exp)
+    assert np.array_equal(got[5][total:], o[5][2][total:])  # (the prefill, untouched)
+    # ranges only: no workspace, no location arguments
+    o2 = [dev.filled(rnd, sh) for sh in shapes[:4]]
+    p2 = [x[1] for x in o2]
+    dev.sync()
+    ix.seeds_batch_async(d_data, d_off, n, *p2, max_seeds=ms, min_len=5, skip=1)
+    ix.sync()
+    got2 = [dev.get(x[0], np.uint32).reshape(sh) for x, sh in zip(o2, shapes)]
+    compare(got2, exp, locate=False)
+    assert all(np.array_equal(a, b) for a, b in zip(got2, got))
+    # argument checks
+    for kw in (dict(max_seeds=0), dict(max_seeds=33)):
+        with pytest.raises(pkg.FmxError) as e:
+            ix.seeds_batch_async(d_data, d_off, n, *p2, **kw)
+        assert e.value.code == pkg._native.FMX_E_ARG
+    with pytest.raises(pkg.FmxError) as e:
+        ix.seeds_batch_async(d_data, d_off, n, 0, *p2[1:], max_seeds=ms)
+    assert e.value.code == pkg._native.FMX_E_ARG
+    # a fixed-length hint the offsets disagree with
+    ix.seeds_batch_async(d_data, d_off, n, *p2, max_seeds=ms, fixed_len=7)
+    with pytest.raises(pkg.FmxError) as e:
+        ix.sync()
+    assert e.value.code == pkg._native.FMX_E_ARG
+    ix.close()

@@ -32,10 +32,10 @@ import _approx_cases as AC
 import _seed_cases as SC
 from _guard_cases import FILL_OUT, Arena
 from _match_cases import ABSENT
+from _util import SIMT_LAYOUTS as LAYOUTS  # noqa: F401
 
 QUERIES = ("match", "seeds", "approx")
 PER = 3  # max_seeds / max_hits: a 256-slot tile straddles the 128-read tile edge
-LAYOUTS = [(4, 3, 64), (8, 2, 32), (4, 5, 128), (8, 4, 64)]
 BOTH_SIZES = (1, 127, 128, 129, 300)
 RC_SIZES = (1, 255, 256, 257)
 FIXED_M = 24

@@ -1,12 +1,18 @@
 """Shared test helpers: random data in the shape of the reference's own
 generators (sview-fmindex/src/tests/random_data/mod.rs:7-37, seeded here), and
 a brute-force occurrence finder (the reference's accuracy contract,
-src/tests/get_accurate_result/mod.rs:136-140)."""
+src/tests/get_accurate_result/mod.rs:136-140).  Below them, what the emulator
+and GPU twins of a query's tests share whatever the query: an index opened
+beside its oracle, one cached text per alphabet, and the two device memories
+(HostDev, TorchDev) their device-call scenarios run over."""
 import numpy as np
 
 # every (P bytes, planes, vector bits) the reference's tests sweep
 # (get_accurate_result/mod.rs:179-222)
 ALL_LAYOUTS = [(p, n, v) for p in (4, 8) for n in (2, 3, 4, 5, 6) for v in (32, 64, 128)]
+# the few the emulator modules visit: u32 and u64 positions, every vector width, symbol-mask, paired and plain
+# records among them
+SIMT_LAYOUTS = [(4, 3, 64), (8, 2, 32), (4, 5, 128), (8, 4, 64)]
 
 
 def table_from_symbols(symbols, with_wildcard=False):
@@ -108,3 +114,92 @@ def random_workspace_jobs(pkg, ix, orc, rng, text, sizes, length):
                                   fixed_len=m))
         bats.append(b)
     return bats, jobs
+
+
+# ---------------------------------------------- an index and its oracle, per case
+
+def pos_of(pkg, pb):
+    return pkg.u32 if pb == 4 else pkg.u64
+
+
+def block_of(pkg, planes, vb):
+    return getattr(pkg.blocks, f"Block{planes}")(pkg.Vector(vb))
+
+
+def open_index(pkg, O, case, pb, planes, vb, occ):
+    """(the index loaded with options `occ`, the oracle over the same blob)."""
+    blob = case.blob(O, pb, planes, vb)
+    orc = O.OracleIndex(blob, O.layout(pb, planes, vb, 0))
+    return pkg.FmIndex.load(blob, pos_of(pkg, pb), block_of(pkg, planes, vb), options=occ), orc
+
+
+_CASES = {}
+
+
+def case_for(planes, two_letters=False, **kw):
+    """One text per alphabet size (_match_cases.Case; its expected values are
+    computed once and shared by every test of the run)."""
+    from _match_cases import Case  # (it imports this module)
+    key = (planes, two_letters, tuple(sorted(kw.items())))
+    if key not in _CASES:
+        nchars = 2 if two_letters else min((1 << planes) - 1, 20)
+        _CASES[key] = Case(planes * 11 + (5 if two_letters else 0), nchars, **kw)
+    return _CASES[key]
+
+
+# ------------------------------------------------------------ device memories
+
+class _Dev:
+    """What the device-call scenarios need of a device memory: put(array) ->
+    (handle, pointer), get(handle, dtype) -> a flat host array, sync(), and
+    `stream`, the hipStream_t to launch on (0: the index's own)."""
+    stream = 0
+
+    def filled(self, rnd, shape, dtype=np.uint32):
+        """A buffer of random values from `rnd`: (handle, pointer, the host
+        copy, kept so that what a launch must leave alone can be checked)."""
+        a = rnd.integers(1, 2**31, shape).astype(dtype)
+        return self.put(a) + (a,)
+
+    def workspace(self, rnd, nbytes):
+        """Random bytes (a workspace needs no initialisation), 256-byte
+        aligned: (handle, pointer)."""
+        h, p = self.put(rnd.integers(0, 256, nbytes + 256).astype(np.uint8))
+        return h, p + (-p) % 256
+
+
+class HostDev(_Dev):
+    """The emulator: device memory is host memory."""
+
+    def put(self, a):
+        a = np.ascontiguousarray(a).copy()
+        return a, a.ctypes.data
+
+    def get(self, h, dtype):
+        return h.view(np.uint8).reshape(-1).view(dtype)
+
+    def sync(self):
+        pass
+
+
+class TorchDev(_Dev):
+    """The GPU: one uint8 tensor per array.  caller_stream: launch on a
+    torch.cuda.Stream of the test's own."""
+
+    def __init__(self, caller_stream=False):
+        import torch
+        self.torch = torch
+        if caller_stream:
+            self._stream = torch.cuda.Stream()
+            self.stream = self._stream.cuda_stream
+
+    def put(self, a):
+        a = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+        t = self.torch.from_numpy(a.copy() if a.size else np.zeros(16, np.uint8)).to("cuda:0")
+        return t, t.data_ptr()
+
+    def get(self, h, dtype):
+        return h.cpu().numpy().view(dtype)
+
+    def sync(self):
+        self.torch.cuda.synchronize()  # (buffers are made on torch's stream; the index launches on its own)

@@ -1,5 +1,5 @@
 """Placing reads (fmx_vote_async, fmx_place_batch): the model, the synthetic
-batches and the runs that the emulator tests (test_vote_simt.py,
+batches, the runs and the cases' bodies that the emulator tests (test_vote_simt.py,
 test_vote_guard_simt.py) and the GPU tests (test_gpu_vote.py,
 test_gpu_vote_guard.py) share.
 
@@ -20,7 +20,9 @@ import numpy as np
 import pytest
 
 from _guard_cases import Arena
-from _seed_cases import expected_arrays
+from _seed_cases import BATCH_SIZES, batch, case_for, expected_arrays, open_index  # noqa: F401
+from _strand_cases import expand, involution
+from _util import HostDev, TorchDev  # noqa: F401
 
 MAX_HITS, OVERFLOW, MORE = 1024, 1, 2
 CHAIN_COUNTS = (1, 3, 4, 5, 255, 256, 257)
@@ -217,41 +219,6 @@ def assert_classes(arrays, ms, pb, band, min_cover, K, exp):
         assert (locs[:cap] >= 1 << 32).any() and ((locs[:cap] < 1 << 32) & (locs[:cap] >= (1 << 32) - 1000)).any()
 
 
-# ------------------------------------------------------------ device memories
-
-class HostDev:
-    """The emulator: device memory is host memory."""
-
-    def put(self, a):
-        a = np.ascontiguousarray(a).copy()
-        return a, a.ctypes.data
-
-    def get(self, h, dtype):
-        return h.view(np.uint8).reshape(-1).view(dtype)
-
-    def sync(self):
-        pass
-
-
-class TorchDev:
-    """The GPU: one uint8 tensor per array."""
-
-    def __init__(self):
-        import torch
-        self.torch = torch
-
-    def put(self, a):
-        a = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
-        t = self.torch.from_numpy(a.copy() if a.size else np.zeros(16, np.uint8)).to("cuda:0")
-        return t, t.data_ptr()
-
-    def get(self, h, dtype):
-        return h.cpu().numpy().view(dtype)
-
-    def sync(self):
-        self.torch.cuda.synchronize()  # (the index launches on its own stream)
-
-
 def vote_device(dev, ix, n, ms, d_ns, d_spans, d_off, d_locs, cap, band, min_cover, K):
     """fmx_vote_async over device pointers into outputs prefilled with -1;
     returns (ncands, flags, pos, cover, mask)."""
@@ -401,6 +368,83 @@ def check_arguments(pkg, dev, ix, pb):
     got = [dev.get(h, dt) for (h, _), dt in zip(outs[:2], (np.uint32, np.uint32))]
     assert (got[0] == 0).all() and np.array_equal(got[1], np.where(off[ms::ms] > 0, OVERFLOW, 0))
     ix.close()
+
+
+# ------------------------------------------------------------------ the cases
+
+def synthetic(dev, ix, n, pb):
+    """Every CONFIGS class over a batch of n synthetic chains."""
+    for ms, band, mc, K in CONFIGS:
+        arrays = make_batch(n, ms, pb, band, K)
+        exp = model(*arrays[:4], ms, arrays[4], band, mc, K)
+        assert_classes(arrays, ms, pb, band, mc, K, exp)
+        got = run_vote(dev, ix, arrays, ms, band, mc, K)
+        compare(f"vote n={n} max_seeds={ms} band={band} min_cover={mc} max_cands={K}", got, exp)
+
+
+def place_runs(dev, pkg, ix, orc, case, pb, n, runs):
+    """place_batch against the model, and against seeds_batch_async +
+    vote_async run here on buffers of the test's own."""
+    pats = batch(case, n)
+    for skip, band, rev in runs:
+        exp, got = check_place(ix, orc, case, pats, skip, band, rev)
+        if n >= 255:
+            assert (exp[0] > 1).sum() >= 20 and (exp[0] == 0).sum() >= 2 and (exp[5] > exp[0]).sum() >= 1
+        if not rev:
+            dgot = place_device(dev, pkg, ix, pb, pats, skip, band)
+            compare("seeds_batch_async + vote_async", dgot, exp)
+
+
+def two_letters(pkg, O, sizes):
+    """A two-letter text: most seeds have more than max_occ occurrences and
+    bring none, the others bring up to 16 each."""
+    case = case_for(2, two_letters=True, k=3, sr=2)
+    ix, orc = open_index(pkg, O, case, 4, 2, 64, 1)
+    for n in sizes:
+        exp, _ = check_place(ix, orc, case, batch(case, n), 1, 8)
+        assert (exp[0] > 0).sum() >= 50
+        check_place(ix, orc, case, batch(case, n), 0, 0, True, max_cands=16, min_cover=1)
+    ix.close()
+
+
+def both_strands(pkg, O, sizes):
+    case = case_for(3, k=3, sr=2)
+    ix, orc = open_index(pkg, O, case, 4, 3, 64, 1)
+    cmap = involution(case)
+    ix.set_complement(cmap)
+    for n in sizes:
+        reads = batch(case, n)
+        both = ix.place_batch(reads, skip=1, band=8, strands="both", **PLACE)
+        flat = ix.place_batch(expand(reads, cmap, "both"), skip=1, band=8, **PLACE)
+        assert both[0].shape == (2 * n,) and all(np.array_equal(a, b) for a, b in zip(both, flat))
+    assert ix.place(reads[3], strands="both") == (ix.place(reads[3]), ix.place(expand(reads[3:4], cmap, "reverse")[0]))
+    ix.close()
+
+
+def chunks_and_limits(pkg, O, monkeypatch):
+    """FMX_PLACE_CHUNK=100 (read at load): 700 reads in seven chunks, the
+    results those of one; max_seeds * max_occ = 1,024 is accepted, 1,025 is
+    FMX_E_ARG."""
+    case = case_for(3, k=3, sr=2)
+    pats = batch(case, 700)
+    ix, orc = open_index(pkg, O, case, 4, 3, 64, 1)
+    whole = ix.place_batch(pats, skip=1, band=8, **PLACE)
+    ix.close()
+    monkeypatch.setenv("FMX_PLACE_CHUNK", "100")
+    ix, orc = open_index(pkg, O, case, 4, 3, 64, 1)
+    check_place(ix, orc, case, pats, 1, 8)
+    parts = ix.place_batch(pats, skip=1, band=8, **PLACE)
+    assert all(np.array_equal(a, b) for a, b in zip(whole, parts))
+    check_limits(pkg, ix, pats[:40])
+    ix.close()
+
+
+def planted(pkg, O, layouts):
+    case = case_for(3, k=3, sr=2)
+    for pb, planes, vb in layouts:
+        ix, orc = open_index(pkg, O, case, pb, planes, vb, 1)
+        check_planted(ix, orc, case)
+        ix.close()
 
 
 # ---------------------------------------------------------------- guard bands
