@@ -119,6 +119,19 @@ typedef struct fmx_layout {
  * load time, paid back only after ~10^10 patterns (bench.py "derived"). */
 #define FMX_OPT_DERIVED (FMX_OCC_INTERLEAVED | FMX_OPT_DEEP_LUT | FMX_OPT_FULL_SA | FMX_OPT_TEXT | \
                          FMX_OPT_ROW_CONTEXT | FMX_OPT_LUT_ROWS)
+/* The text (n + 16 bytes of symbol indices, the buffer of FMX_OPT_TEXT) kept in
+ * HBM for fmx_verify_async / fmx_map_batch ONLY: no search reads it, and the
+ * index stays the one the other options make — with FMX_OPT_DEFAULT still the
+ * faithful one: grouped and fused launches, every query's path and bytes, and
+ * everything fmx_info reports but `options` (this bit, when the text is held)
+ * and `device_bytes` (+ n + 16) are unchanged.  Not part of FMX_OPT_DERIVED.
+ * The text is recovered through the full suffix array: without FMX_OPT_FULL_SA
+ * / FMX_OPT_TEXT that array is a temporary of the load, freed before it
+ * returns — the load's PEAK HBM is n * P + 64 bytes (4 GB at 1 Gbp and u32
+ * positions) above what the loaded index keeps.  With them the array stays and
+ * the one text buffer is shared.  (An index loaded with FMX_OPT_TEXT serves
+ * the verify calls without this bit.) */
+#define FMX_OPT_VERIFY_TEXT 64u
 /* fmx_load_file only: read the blob's body with O_DIRECT, bypassing the page
  * cache — a cold load from storage, what the reference bench measures after
  * dropping the caches (bench/run_benchmark.sh:53-56).  FMX_E_ARG if the
@@ -646,6 +659,78 @@ fmx_status fmx_place_batch(fmx_index *ix, const uint8_t *bytes, const uint64_t *
                            uint32_t *out_ncands, uint32_t *out_flags,
                            int64_t *out_pos, uint32_t *out_cover, uint32_t *out_mask);
 
+/* ----------------------------------------------------- verifying placements
+ * What a read mapper does with a candidate: align the read against the text
+ * around it, to learn whether the candidate is real, how many edits it costs
+ * and where the alignment starts and ends (no reference counterpart).  Added
+ * within ABI 8: FMX_ABI_VERSION is unchanged.  The index must hold the text:
+ * FMX_OPT_VERIFY_TEXT (or FMX_OPT_TEXT) at load.
+ * fmx_verify_async takes the reads exactly as a seeds launch takes them —
+ * FMX_PATTERN_REVERSED, FMX_PATTERN_REVCOMP and FMX_BOTH_STRANDS mean what
+ * they mean there (nv = 2n virtual patterns v = 2i + s under the last); the
+ * staging and fixed-length hints are accepted and ignored, the kernel always
+ * reads the offsets — and the candidates fmx_vote_async wrote for those nv
+ * chains at max_cands (1..16): d_ncands[nv], d_pos[nv * max_cands].  An
+ * ncands[v] above max_cands counts as max_cands.
+ * Per candidate slot c = v * max_cands + k: q[0..m) is virtual pattern v as
+ * symbol indices in its logical order (strand 0: q[i] = enc[p[i]], strand 1:
+ * q[i] = enc_rc[p[m-1-i]]), t[0..n) the text's symbol indices, P = pos[c]
+ * (it may be negative).  Cells (i, j), 0 <= i <= m, are ALLOWED when j is in
+ * A(i) = [max(0, i+P-band), min(n, i+P+band)]: the diagonals within `band` of
+ * the candidate's, inside the text.  Unit costs: a substitution, an insertion
+ * and a deletion cost 1 each; symbols compare by index, and a q[i] >=
+ * symbol_count never matches.
+ * FORWARD: F[0][j] = 0 on A(0); F[i][j] = min(F[i-1][j-1] + [q[i-1] != t[j-1]],
+ * F[i-1][j] + 1, F[i][j-1] + 1) over allowed predecessors, infinite with none;
+ * D = min over A(m) of F[m][j], tend = the smallest j attaining it.
+ * BACKWARD (the same cells and costs, anchored): G[m][tend] = 0; G[i][j] =
+ * min(G[i+1][j+1] + [q[i] != t[j]], G[i+1][j] + 1, G[i][j+1] + 1); tstart =
+ * the largest j in A(0) with G[0][j] = D (one exists: both passes range over
+ * the same paths).  So q aligns to t[tstart..tend) at cost D: the shortest of
+ * the cheapest alignments that end at the earliest cheapest end.
+ * OUTPUTS, fully defined: k < ncands[v], D finite and <= max_dist: dist[c] =
+ * D, tstart[c], tend[c].  k < ncands[v] and D infinite, or D > max_dist, or
+ * m > FMX_VERIFY_MAX_LEN: dist[c] = FMX_VERIFY_NONE, tstart = tend = 0.
+ * k >= ncands[v]: three zeros.  (The row minimum of F never decreases with i:
+ * a candidate is dropped at the first row whose minimum exceeds max_dist.)
+ * m = 0 follows the rules as written: D = 0 when A(0) is not empty.
+ * Sizes and alignment: the rule of the device calls above — nv words for
+ * d_ncands, nv max_cands elements for d_pos, d_tstart, d_tend (8-B aligned)
+ * and d_dist (4); d_bytes and d_offsets as for seeds.  No workspace, and
+ * nothing is latched in the status word.  n_patterns = 0 is FMX_OK and
+ * launches nothing.  FMX_E_ARG: an index that holds no text, band >
+ * FMX_VERIFY_MAX_BAND, max_cands outside 1..16, strand flags misused (as for
+ * seeds), a null or misaligned pointer, more slots than a launch's 2^31 - 1
+ * workgroups of four hold.
+ * One kernel, k_verify: a wavefront per candidate slot, lane k <= 2 band
+ * owning diagonal P - band + k, a row of F per step — the read's symbols
+ * fetched 64 at a time and broadcast, the text shifted along the lanes, the
+ * in-row term a prefix-min scan over the lanes —, both passes one routine; no
+ * LDS, no barrier.  Timer: "verify", one unit per candidate slot. */
+#define FMX_VERIFY_MAX_BAND 31u
+#define FMX_VERIFY_MAX_LEN  65535u
+#define FMX_VERIFY_NONE     0xFFFFFFFFu
+fmx_status fmx_verify_async(fmx_index *ix, const uint8_t *d_bytes, const uint64_t *d_offsets,
+                            uint64_t n_patterns, uint32_t flags,
+                            uint32_t max_cands, const uint32_t *d_ncands, const int64_t *d_pos,
+                            uint32_t band, uint32_t max_dist,
+                            uint32_t *d_dist, int64_t *d_tstart, int64_t *d_tend, void *stream);
+
+/* Host buffers, synchronous: fmx_place_batch with the verify launch appended
+ * on the same stream, in the same chunk loop (the reads are already in the
+ * chunk's HBM; FMX_PLACE_CHUNK applies).  The first five outputs are exactly
+ * fmx_place_batch's for the same arguments; out_dist, out_tstart and out_tend
+ * (nv * max_cands each) are fmx_verify_async applied to them with align_band
+ * and max_dist.  FMX_E_ARG as for both calls. */
+fmx_status fmx_map_batch(fmx_index *ix, const uint8_t *bytes, const uint64_t *offsets,
+                         uint64_t n_patterns, uint32_t flags,
+                         uint32_t max_seeds, uint32_t min_len, uint32_t skip, uint64_t max_occ,
+                         uint32_t band, uint32_t min_cover, uint32_t max_cands,
+                         uint32_t align_band, uint32_t max_dist,
+                         uint32_t *out_ncands, uint32_t *out_flags,
+                         int64_t *out_pos, uint32_t *out_cover, uint32_t *out_mask,
+                         uint32_t *out_dist, int64_t *out_tstart, int64_t *out_tend);
+
 /* Wait for `stream` and return (and clear) the latched device status. */
 fmx_status fmx_sync(fmx_index *ix, void *stream);
 
@@ -694,7 +779,8 @@ fmx_status fmx_multi_locate_batch(fmx_multi *m, const uint8_t *bytes, const uint
  * several microseconds, so throughput runs sample (k > 1).  Timers: "count",
  * "locate" (a whole locate launch), "match" (a whole match launch), "seeds"
  * (a whole seed-chain launch, a unit per slot), "approx" (a whole k-mismatch
- * launch, a unit per slot), "vote" (k_vote, a unit per chain) and, for
+ * launch, a unit per slot), "vote" (k_vote, a unit per chain), "verify"
+ * (k_verify, a unit per candidate slot) and, for
  * fmx_locate_group_async, its two kernels "locate.search" (k_search) and
  * "locate.emit" (k_emit). */
 fmx_status fmx_timing_enable(fmx_index *ix, int enable);

@@ -44,7 +44,11 @@ from . import distributed  # noqa: F401  (multi-GPU helpers)
 
 __all__ = ["FmIndex", "FmIndexBuilder", "Position", "u32", "u64", "Vector", "blocks",
            "text_encoders", "build_config", "LoadError", "BuildError", "FmxError",
-           "aligned_buffer", "pack_patterns", "complement_map"]
+           "aligned_buffer", "pack_patterns", "complement_map", "OPT_VERIFY_TEXT"]
+
+# load option (OR it into `options`): keep the text in HBM for verify_async / map_batch only; no search reads
+# it and the index stays the one the other options make (FMX_OPT_VERIFY_TEXT, fmx.h)
+OPT_VERIFY_TEXT = _n.FMX_OPT_VERIFY_TEXT
 
 
 # ------------------------------------------------------------------ errors
@@ -775,6 +779,51 @@ class FmIndex:
                "fmx_place_batch")
         return (nc[:n], fl[:n], pos[:n * K].reshape(n, K), cover[:n * K].reshape(n, K), mask[:n * K].reshape(n, K))
 
+    # -- mapping reads: place, then align each candidate against the text (needs the text: OPT_VERIFY_TEXT) --
+    def map(self, pattern: bytes, max_seeds: int = 8, min_len: int = 1, skip: int = 0, max_occ: int = 16,
+            band: int = 0, min_cover: int = 1, max_cands: int = 4, align_band: int = 8,
+            max_dist: Optional[int] = None, strands: str = "forward"):
+        """The read's verified placements, in place()'s order: [(pos, cover,
+        mask, dist, tstart, tend)] — the read aligns to text[tstart:tend] at
+        `dist` unit-cost edits; dist is None (tstart = tend = 0) for a candidate
+        with no alignment within align_band diagonals of pos and max_dist
+        edits.  strands="both": a (forward, reverse) pair of such lists."""
+        nc, _, pos, cover, mask, dist, ts, te = self.map_batch([pattern], max_seeds, min_len, skip, max_occ, band,
+                                                               min_cover, max_cands, align_band, max_dist,
+                                                               strands=strands)
+        res = [[(int(pos[v, k]), int(cover[v, k]), int(mask[v, k]),
+                 None if dist[v, k] == _n.FMX_VERIFY_NONE else int(dist[v, k]), int(ts[v, k]), int(te[v, k]))
+                for k in range(int(nc[v]))] for v in range(nc.size)]
+        return tuple(res) if strands == "both" else res[0]
+
+    def map_batch(self, patterns, max_seeds: int = 8, min_len: int = 1, skip: int = 0, max_occ: int = 16,
+                  band: int = 0, min_cover: int = 1, max_cands: int = 4, align_band: int = 8,
+                  max_dist: Optional[int] = None, reversed: bool = False, strands: str = "forward"):
+        """place_batch, then every candidate aligned against the text on the
+        device (fmx_map_batch): place_batch's five arrays, then dist
+        uint32[n, max_cands], tstart, tend int64[n, max_cands].  Candidate k of
+        read v aligns to text[tstart:tend] at dist edits (substitutions,
+        insertions, deletions, 1 each), over the diagonals within align_band
+        (0..31) of pos: the fewest edits, the earliest end among those, the
+        shortest alignment to that end.  dist = 0xFFFFFFFF (tstart = tend = 0):
+        no alignment within the band, or more than max_dist edits (None: any
+        number), or a read longer than 65,535; unused entries are zero.  The
+        index must hold the text: load it with options | OPT_VERIFY_TEXT."""
+        data, offsets = patterns if isinstance(patterns, tuple) else pack_patterns(patterns)
+        reads, K = offsets.size - 1, int(max_cands)
+        n = 2 * reads if strands == "both" else reads
+        rows = max(n, 1) * max(K, 1)
+        nc, fl = np.zeros(max(n, 1), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.uint32)
+        pos, ts, te = (np.zeros(rows, dtype=np.int64) for _ in range(3))
+        cover, mask, dist = (np.zeros(rows, dtype=np.uint32) for _ in range(3))
+        flags = (_n.FMX_PATTERN_REVERSED if reversed else 0) | _strand_flags(strands)
+        _check(_n.lib().fmx_map_batch(self._h, _ptr(data) if data.size else None, _ptr(offsets), reads, flags,
+                                      int(max_seeds), int(min_len), int(skip), int(max_occ), int(band), int(min_cover),
+                                      K, int(align_band), _n.FMX_VERIFY_NONE - 1 if max_dist is None else int(max_dist),
+                                      _ptr(nc), _ptr(fl), _ptr(pos), _ptr(cover), _ptr(mask), _ptr(dist), _ptr(ts),
+                                      _ptr(te)), "fmx_map_batch")
+        return (nc[:n], fl[:n]) + tuple(a[:n * K].reshape(n, K) for a in (pos, cover, mask, dist, ts, te))
+
     # -- device-resident API (pointers are ints; stream is a hipStream_t) --
     def count_batch_async(self, d_bytes: int, d_offsets: int, n: int, d_counts: int,
                           stream: int = 0, reversed: bool = False, long_patterns: bool = False, stage_kb: int = 0,
@@ -871,6 +920,22 @@ class FmIndex:
             self._h, n_chains, int(max_seeds), _vp(d_nseeds), _vp(d_spans), _vp(d_loc_offsets), _vp(d_locs), cap,
             int(band), int(min_cover), int(max_cands), _vp(d_ncands), _vp(d_flags), _vp(d_pos), _vp(d_cover),
             _vp(d_mask), _vp(stream)))
+
+    def verify_async(self, d_bytes: int, d_offsets: int, n: int, d_ncands: int, d_pos: int, d_dist: int,
+                     d_tstart: int, d_tend: int, max_cands: int = 4, band: int = 8, max_dist: Optional[int] = None,
+                     stream: int = 0, reversed: bool = False, long_patterns: bool = False, stage_kb: int = 0,
+                     fixed_len: int = 0, strands: str = "forward") -> None:
+        """fmx_verify_async: the reads as seeds_batch_async takes them (the
+        staging hints are ignored) and what vote_async left for their chains —
+        2n under strands="both" — at max_cands: d_ncands uint32[n], d_pos
+        int64[n max_cands]; d_dist uint32[n max_cands], d_tstart, d_tend
+        int64[n max_cands] (map_batch describes them).  No workspace; on the
+        same stream as the vote no synchronisation is needed in between."""
+        flags = _flags(reversed, long_patterns, stage_kb, fixed_len) | _strand_flags(strands)
+        _check(_n.lib().fmx_verify_async(
+            self._h, C.c_void_p(d_bytes), C.c_void_p(d_offsets), n, flags, int(max_cands), _vp(d_ncands), _vp(d_pos),
+            int(band), _n.FMX_VERIFY_NONE - 1 if max_dist is None else int(max_dist), _vp(d_dist), _vp(d_tstart),
+            _vp(d_tend), _vp(stream)))
 
     @staticmethod
     def locate_job(d_bytes: int, d_offsets: int, n: int, d_loc_offsets: int, d_locs: int, cap: int,

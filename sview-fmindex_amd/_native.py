@@ -34,6 +34,9 @@ FMX_APPROX_BEST = 1
 FMX_VOTE_MAX_HITS = 1024
 FMX_VOTE_OVERFLOW = 1
 FMX_VOTE_MORE = 2
+FMX_VERIFY_MAX_BAND = 31
+FMX_VERIFY_MAX_LEN = 65535
+FMX_VERIFY_NONE = 0xFFFFFFFF
 FMX_OCC_BLOB = 0
 FMX_OCC_INTERLEAVED = 1
 FMX_OPT_DEEP_LUT = 2
@@ -44,6 +47,7 @@ FMX_OPT_LUT_ROWS = 32
 FMX_OPT_DEFAULT = FMX_OCC_INTERLEAVED
 FMX_OPT_DERIVED = (FMX_OCC_INTERLEAVED | FMX_OPT_DEEP_LUT | FMX_OPT_FULL_SA | FMX_OPT_TEXT | FMX_OPT_ROW_CONTEXT
                    | FMX_OPT_LUT_ROWS)
+FMX_OPT_VERIFY_TEXT = 64
 FMX_LOAD_DIRECT = 1 << 16
 
 
@@ -114,6 +118,9 @@ SIGNATURES = {
                                     _p, _u64, _p]),
     "fmx_vote_async": (_i, [_p, _u64, _u32, _p, _p, _p, _p, _u64, _u32, _u32, _u32, _p, _p, _p, _p, _p, _p]),
     "fmx_place_batch": (_i, [_p, _p, _p, _u64, _u32, _u32, _u32, _u32, _u64, _u32, _u32, _u32, _p, _p, _p, _p, _p]),
+    "fmx_verify_async": (_i, [_p, _p, _p, _u64, _u32, _u32, _p, _p, _u32, _u32, _p, _p, _p, _p]),
+    "fmx_map_batch": (_i, [_p, _p, _p, _u64, _u32, _u32, _u32, _u32, _u64, _u32, _u32, _u32, _u32, _u32, _p, _p, _p, _p,
+                           _p, _p, _p, _p]),
     "fmx_sync": (_i, [_p, _p]),
     "fmx_stream_release": (_i, [_p, _p]),
     "fmx_multi_load": (_i, [_p, _u64, fmx_layout, C.POINTER(_i), _i, _u32, C.POINTER(_p), _PU64, _PU64]),

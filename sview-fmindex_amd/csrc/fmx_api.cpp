@@ -635,7 +635,8 @@ static fmx_status finish_load(fmx_index *ix, uint32_t options) {
         // multi-line symbol masks only for the faithful index (no derived
         // structures); if their records do not fit in HBM, the one-line
         // encodings, and if those do not fit either, the blob layout
-        uint32_t rec = interleaved_record_bytes(v, (options & ~FMX_OCC_INTERLEAVED) == 0);
+        // (FMX_OPT_VERIFY_TEXT adds nothing a search reads: the index stays faithful)
+        uint32_t rec = interleaved_record_bytes(v, (options & ~(FMX_OCC_INTERLEAVED | FMX_OPT_VERIFY_TEXT)) == 0);
         // (FMX_OCC_MAX_MB caps the records' HBM: the same fallback, testable)
         const char *cap_env = getenv("FMX_OCC_MAX_MB");
         const uint64_t cap = cap_env ? strtoull(cap_env, nullptr, 10) << 20 : ~0ull;
@@ -753,6 +754,26 @@ static fmx_status finish_load(fmx_index *ix, uint32_t options) {
         if (build_dlut_rows(ix, ix->stream) != hipSuccess) return FMX_E_DEVICE;
         q.dlut_rows = 1;
         ix->options |= FMX_OPT_LUT_ROWS;
+    }
+    // the text for fmx_verify_async alone: q.text and q.safull stay what the other options made them, so no
+    // search sees it.  Without a full SA of the options' own one is built, read by build_text and freed again.
+    if ((options & FMX_OPT_VERIFY_TEXT) && v.n > 0) {
+        if (!ix->d_text) {
+            const bool temp_sa = ix->d_safull == nullptr;
+            if (temp_sa) {
+                q.sa_stride = 1;  // (build_text reads it)
+                if (build_full_sa(ix, 1, ix->stream, true) != hipSuccess) return FMX_E_DEVICE;
+            }
+            const hipError_t e = build_text(ix, ix->stream);
+            if (temp_sa) {
+                hipFree(ix->d_safull);
+                ix->d_safull = nullptr;
+                ix->safull_bytes = 0;
+                q.sa_stride = 0;
+            }
+            if (e != hipSuccess) return FMX_E_DEVICE;
+        }
+        ix->options |= FMX_OPT_VERIFY_TEXT;
     }
     return FMX_OK;
 }
@@ -1317,6 +1338,34 @@ fmx_status fmx_vote_async(fmx_index *ix, uint64_t n, uint32_t max_seeds, const u
     return dev_err(timed(ix, "vote", s, n, [&](hipEvent_t) { return launch_vote(ix, vb, s); }));
 }
 
+// band and max_cands in range, an index that holds the text, and a slot count (nv * max_cands) whose
+// workgroups of four a launch takes
+static bool verify_shape_ok(const fmx_index *ix, uint64_t nv, uint32_t max_cands, uint32_t band) {
+    return ix->d_text && band <= FMX_VERIFY_MAX_BAND && max_cands >= 1 && max_cands <= kVoteMaxCands &&
+           nv <= 4 * 0x7FFFFFFFull / max_cands;
+}
+
+// The banded alignment of a vote's candidates.  Nothing is latched: no status word is taken.
+fmx_status fmx_verify_async(fmx_index *ix, const uint8_t *d_bytes, const uint64_t *d_offsets, uint64_t n,
+                            uint32_t flags, uint32_t max_cands, const uint32_t *d_ncands, const int64_t *d_pos,
+                            uint32_t band, uint32_t max_dist, uint32_t *d_dist, int64_t *d_tstart, int64_t *d_tend,
+                            void *stream) {
+    if (!ix || !strand_flags_ok(ix, flags) || !virtual_patterns(n, flags, &n)) return FMX_E_ARG;  // (n: virtual)
+    if (!verify_shape_ok(ix, n, max_cands, band)) return FMX_E_ARG;
+    if (n == 0) return FMX_OK;
+    if (!d_bytes || !d_offsets || !d_ncands || !d_pos || !d_dist || !d_tstart || !d_tend) return FMX_E_ARG;
+    const auto misaligned = [](const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; };
+    if (misaligned(d_offsets, 8) || misaligned(d_ncands, 4) || misaligned(d_pos, 8) || misaligned(d_dist, 4) ||
+        misaligned(d_tstart, 8) || misaligned(d_tend, 8))
+        return FMX_E_ARG;
+    hipStream_t s = stream ? (hipStream_t)stream : ix->stream;
+    DeviceGuard dg(ix->device);
+    const VerifyBatch vb{n,      ix->bv.n,      ix->d_text,   ix->d_tab, d_bytes, d_offsets,  d_ncands,
+                         d_pos,  flags_rev(flags), flags & kStrandFlags, ix->bv.sigma, max_cands, band, max_dist,
+                         d_dist, d_tstart,      d_tend};
+    return dev_err(timed(ix, "verify", s, n * max_cands, [&](hipEvent_t) { return launch_verify(ix, vb, s); }));
+}
+
 fmx_status fmx_locate_jobs_async(fmx_index *ix, const fmx_locate_job *jobs, uint64_t n_jobs) {
     if (!ix || (n_jobs && !jobs)) return FMX_E_ARG;
     for (uint64_t i = 0; i < n_jobs; ++i) {
@@ -1684,16 +1733,25 @@ fmx_status fmx_approx_batch(fmx_index *ix, const uint8_t *bytes, const uint64_t 
 // at most ix->place_chunk reads at a time; of every chunk only its reads go up
 // and its candidates come down.  The seeds launch gets room for max_occ
 // locations per slot — no seed reports more —, so it cannot run short and no
-// chain's offsets reach past it; no retry.
-fmx_status fmx_place_batch(fmx_index *ix, const uint8_t *bytes, const uint64_t *offsets, uint64_t n, uint32_t flags,
-                           uint32_t max_seeds, uint32_t min_len, uint32_t skip, uint64_t max_occ, uint32_t band,
-                           uint32_t min_cover, uint32_t max_cands, uint32_t *out_ncands, uint32_t *out_flags,
-                           int64_t *out_pos, uint32_t *out_cover, uint32_t *out_mask) {
+// chain's offsets reach past it; no retry.  With `map` (fmx_map_batch) the
+// verify launch follows the vote on the chunk's reads and candidates where they
+// lie, and its three outputs come down with the vote's five.
+struct MapArgs {
+    uint32_t band, max_dist;
+    uint32_t *out_dist;
+    int64_t *out_tstart, *out_tend;
+};
+static fmx_status place_chunks(fmx_index *ix, const uint8_t *bytes, const uint64_t *offsets, uint64_t n, uint32_t flags,
+                               uint32_t max_seeds, uint32_t min_len, uint32_t skip, uint64_t max_occ, uint32_t band,
+                               uint32_t min_cover, uint32_t max_cands, uint32_t *out_ncands, uint32_t *out_flags,
+                               int64_t *out_pos, uint32_t *out_cover, uint32_t *out_mask, const MapArgs *map) {
     uint64_t nv;  // the virtual patterns: the outputs' shape
     if (!ix || !strand_flags_ok(ix, flags) || !virtual_patterns(n, flags, &nv)) return FMX_E_ARG;
     if (!vote_shape_ok(ix, max_seeds, max_cands) || !slots_shape_ok(nv, max_seeds, kMaxSeeds)) return FMX_E_ARG;
     if (max_occ > kVoteMaxHits / max_seeds) return FMX_E_ARG;
+    if (map && !verify_shape_ok(ix, nv, max_cands, map->band)) return FMX_E_ARG;
     if (n && (!offsets || !out_ncands || !out_flags || !out_pos || !out_cover || !out_mask)) return FMX_E_ARG;
+    if (n && map && (!map->out_dist || !map->out_tstart || !map->out_tend)) return FMX_E_ARG;
     if (n == 0) return FMX_OK;
     if (!offsets_ok(bytes, offsets, n)) return FMX_E_ARG;
     const uint64_t pb = ix->bv.L.pos_bytes, per = nv / n, K = max_cands;
@@ -1706,6 +1764,9 @@ fmx_status fmx_place_batch(fmx_index *ix, const uint8_t *bytes, const uint64_t *
         const uint64_t o_nc = c.add(cv * 4, out_ncands + v0), o_fl = c.add(cv * 4, out_flags + v0);
         const uint64_t o_pos = c.add(cv * K * 8, out_pos + v0 * K), o_cov = c.add(cv * K * 4, out_cover + v0 * K);
         const uint64_t o_mask = c.add(cv * K * 4, out_mask + v0 * K);
+        const uint64_t o_dist = map ? c.add(cv * K * 4, map->out_dist + v0 * K) : 0;
+        const uint64_t o_ts = map ? c.add(cv * K * 8, map->out_tstart + v0 * K) : 0;
+        const uint64_t o_te = map ? c.add(cv * K * 8, map->out_tend + v0 * K) : 0;
         // temporary: what the seeds launch writes and the vote reads
         const uint64_t o_ns = c.add(cv * 4), o_rest = c.add(cv * 4), o_span = c.add(2 * slots * 4);
         const uint64_t o_rng = c.add(2 * slots * pb), o_loff = c.add((slots + 1) * 8), o_need = c.add(8);
@@ -1720,14 +1781,36 @@ fmx_status fmx_place_batch(fmx_index *ix, const uint8_t *bytes, const uint64_t *
                                           (uint32_t *)(d + o_span), d + o_rng, (uint64_t *)(d + o_loff), d + o_locs,
                                           cap, (uint64_t *)(d + o_need), ix->d_ws, ix->ws_bytes, s);
                 if (e) return e;
-                return fmx_vote_async(ix, cv, max_seeds, (uint32_t *)(d + o_ns), (uint32_t *)(d + o_span),
-                                      (uint64_t *)(d + o_loff), d + o_locs, cap, band, min_cover, max_cands,
-                                      (uint32_t *)(d + o_nc), (uint32_t *)(d + o_fl), (int64_t *)(d + o_pos),
-                                      (uint32_t *)(d + o_cov), (uint32_t *)(d + o_mask), s);
+                e = fmx_vote_async(ix, cv, max_seeds, (uint32_t *)(d + o_ns), (uint32_t *)(d + o_span),
+                                   (uint64_t *)(d + o_loff), d + o_locs, cap, band, min_cover, max_cands,
+                                   (uint32_t *)(d + o_nc), (uint32_t *)(d + o_fl), (int64_t *)(d + o_pos),
+                                   (uint32_t *)(d + o_cov), (uint32_t *)(d + o_mask), s);
+                if (e || !map) return e;
+                return fmx_verify_async(ix, d, (uint64_t *)(d + c.o_off), nc, c.flags, max_cands,
+                                        (uint32_t *)(d + o_nc), (int64_t *)(d + o_pos), map->band, map->max_dist,
+                                        (uint32_t *)(d + o_dist), (int64_t *)(d + o_ts), (int64_t *)(d + o_te), s);
             });
         if (st) return st;
     }
     return FMX_OK;
+}
+
+fmx_status fmx_place_batch(fmx_index *ix, const uint8_t *bytes, const uint64_t *offsets, uint64_t n, uint32_t flags,
+                           uint32_t max_seeds, uint32_t min_len, uint32_t skip, uint64_t max_occ, uint32_t band,
+                           uint32_t min_cover, uint32_t max_cands, uint32_t *out_ncands, uint32_t *out_flags,
+                           int64_t *out_pos, uint32_t *out_cover, uint32_t *out_mask) {
+    return place_chunks(ix, bytes, offsets, n, flags, max_seeds, min_len, skip, max_occ, band, min_cover, max_cands,
+                        out_ncands, out_flags, out_pos, out_cover, out_mask, nullptr);
+}
+
+fmx_status fmx_map_batch(fmx_index *ix, const uint8_t *bytes, const uint64_t *offsets, uint64_t n, uint32_t flags,
+                         uint32_t max_seeds, uint32_t min_len, uint32_t skip, uint64_t max_occ, uint32_t band,
+                         uint32_t min_cover, uint32_t max_cands, uint32_t align_band, uint32_t max_dist,
+                         uint32_t *out_ncands, uint32_t *out_flags, int64_t *out_pos, uint32_t *out_cover,
+                         uint32_t *out_mask, uint32_t *out_dist, int64_t *out_tstart, int64_t *out_tend) {
+    const MapArgs map{align_band, max_dist, out_dist, out_tstart, out_tend};
+    return place_chunks(ix, bytes, offsets, n, flags, max_seeds, min_len, skip, max_occ, band, min_cover, max_cands,
+                        out_ncands, out_flags, out_pos, out_cover, out_mask, &map);
 }
 
 // ---------------------------------------------------------------- timing

@@ -516,6 +516,25 @@ struct VoteBatch {
     uint32_t *out_mask;
 };
 hipError_t launch_vote(const fmx_index *ix, const VoteBatch &vb, hipStream_t stream);
+// k_verify (fmx_verify_async): the banded alignment of nv virtual patterns against the text at each of their
+// max_cands candidate positions.  Of the index it reads the text (fmx_index::d_text) and the byte tables alone.
+struct VerifyBatch {
+    uint64_t nv;           // virtual patterns
+    uint64_t n;            // text length
+    const uint8_t *text;   // symbol indices
+    const QueryTables *tab;
+    const uint8_t *bytes;
+    const uint64_t *offs;
+    const uint32_t *ncands;
+    const int64_t *pos;  // max_cands per virtual pattern, here and in the outputs
+    uint32_t rev;        // FMX_PATTERN_REVERSED
+    uint32_t strands;    // 0, FMX_PATTERN_REVCOMP or FMX_BOTH_STRANDS
+    uint32_t sigma, max_cands, band, max_dist;
+    uint32_t *out_dist;
+    int64_t *out_tstart;
+    int64_t *out_tend;
+};
+hipError_t launch_verify(const fmx_index *ix, const VerifyBatch &vb, hipStream_t stream);
 // `mid` (optional): an event recorded between k_search and k_emit (timing).
 // Fills grp's per-launch fields (first, emit_begin, the grouped fields) in place.
 hipError_t launch_locate_group(const fmx_index *ix, LocateGroup &grp, uint32_t stage_flags,
@@ -664,7 +683,9 @@ hipError_t build_deep_lut(fmx_index *ix, uint32_t K, hipStream_t stream);
 // (FMX_OPT_LUT_ROWS; needs the full SA and the text).
 hipError_t build_dlut_rows(fmx_index *ix, hipStream_t stream);
 // Recover the full suffix array into ix->d_safull (FMX_OPT_FULL_SA).
-hipError_t build_full_sa(fmx_index *ix, uint32_t stride, hipStream_t stream);
+// from_blob: the walk reads the blob's own occ layout whatever records the index holds (FMX_OPT_VERIFY_TEXT's
+// temporary array: the walk is compiled for the blob layout and the records of the derived indexes only).
+hipError_t build_full_sa(fmx_index *ix, uint32_t stride, hipStream_t stream, bool from_blob = false);
 // Recover the text (symbol indices) into ix->d_text from d_safull (FMX_OPT_TEXT).
 hipError_t build_text(fmx_index *ix, hipStream_t stream);
 // Fill the context half of the row records (FMX_OPT_ROW_CONTEXT) from d_text.

@@ -1661,4 +1661,90 @@ __device__ __forceinline__ bool vote_better(uint32_t c1, int64_t p1, uint32_t c2
     return c1 > c2 || (c1 == c2 && p1 < p2);
 }
 
+// ------------------------------------------------------ k_verify's band pass
+// (k_verify itself: fmx_query.hip; the contract: fmx_verify_async, fmx.h.)  A
+// wavefront runs rows 0..m of the band around candidate P, a row per step:
+// lane k <= 2 band owns diagonal P - band + k, in row r the cell (r, j = r + P
+// - band + k), ALLOWED when 0 <= j <= n; every other cell is kVerifyInf.  Of
+// the recurrence's three terms the diagonal one is the lane's own previous
+// value, the vertical one its upper neighbour's (one shuffle, which also shifts
+// the text along the lanes: lane L of all 64 holds t[r - 1 + P - band + L],
+// what lane L + 1 held a row before; the lanes above the band look ahead, and
+// one coalesced load refills the window every 64 - 2 band rows), and the in-row
+// one, F[k] = min over k' <= k of h[k'] + (k - k'), a prefix-min scan of h - k
+// over the band's lanes: ceil(log2(2 band + 1)) shuffle steps.  The read comes
+// 64 symbols at a time, a lane each through the byte table, and is broadcast
+// row by row.
+// back: the same pass over the reversed read and the reversed text — the
+// contract's backward recurrence with P' = n - m - P, j' = n - j and the lanes'
+// diagonals mirrored, so that "the largest j" is again the smallest lane.
+// anchor < 64: row 0 is zero at that lane only (64: wherever allowed).
+// Returns (D << 6) | k: row m's minimum and the smallest lane attaining it; D
+// >= kVerifyInf when no cell of row m can be reached, or — the row minimum
+// never decreases — as soon as a whole row exceeds max_dist.  Every wave
+// operation is reached by all 64 lanes: the branches depend on the row alone.
+constexpr uint32_t kVerifyInf = 1u << 22;  // (cost << 8 | text symbol) is one word; costs stay below 2^17
+constexpr uint32_t kVerifyNoSym = 0xFFu;   // outside the read / the text: matches nothing
+
+struct VerifyRead {
+    const uint8_t *raw;  // the read's bytes
+    const uint8_t *enc;  // the byte table of its strand (QueryTables::enc / enc_rc)
+    uint64_t m;
+    bool rev;  // the bytes run against q's logical order
+    uint32_t sigma;
+};
+
+__device__ __forceinline__ uint32_t verify_pass(const VerifyRead &q, const uint8_t *__restrict__ text, uint64_t n,
+                                                bool back, int64_t P, uint32_t band, uint32_t anchor,
+                                                uint32_t max_dist, uint32_t lane) {
+    const uint32_t W = 2 * band + 1, refill = 64 - 2 * band, m = (uint32_t)q.m;
+    const int64_t d0 = P - (int64_t)band, dk = d0 + (int64_t)lane;
+    const bool qrev = q.rev != back;
+    // a row's costs before the in-row term -> the row: the scan, cells outside the band or the text dropped
+    const auto finish = [&](uint32_t h, uint32_t r) {
+        const int64_t j = (int64_t)r + dk;
+        const bool ok = lane < W && j >= 0 && j <= (int64_t)n;
+        uint32_t g = (ok ? h : kVerifyInf) + 64u - lane;
+        for (uint32_t d = 1; d < W; d <<= 1) {
+            const uint32_t o = __shfl_up(g, d);
+            if (lane >= d && o < g) g = o;
+        }
+        g = g + lane - 64u;
+        return ok && g < kVerifyInf ? g : kVerifyInf;
+    };
+    const auto hopeless = [&](uint32_t f) { return __all(f > max_dist || f >= kVerifyInf) != 0; };
+    uint32_t F = finish(anchor == 64 || lane == anchor ? 0u : kVerifyInf, 0);
+    if (hopeless(F)) return kVerifyInf << 6;
+    uint32_t tw = kVerifyNoSym, qc = kVerifyNoSym, left = 0;
+    for (uint32_t r = 1; r <= m; ++r) {
+        const uint32_t o = __shfl((F << 8) | tw, (int)((lane + 1) & 63));
+        const uint32_t up = o >> 8;  // (lane 2 band's neighbour is outside the band: kVerifyInf)
+        if (left == 0) {
+            const int64_t x = (int64_t)(r - 1) + d0 + (int64_t)lane;
+            tw = x >= 0 && x < (int64_t)n ? text[back ? n - 1 - (uint64_t)x : (uint64_t)x] : kVerifyNoSym;
+            left = refill;
+        } else {
+            tw = o & 0xFFu;
+        }
+        --left;
+        const uint32_t ci = (r - 1) & 63;
+        if (ci == 0) {
+            const uint64_t x = (uint64_t)(r - 1) + lane;
+            qc = x < q.m ? q.enc[q.raw[qrev ? q.m - 1 - x : x]] : kVerifyNoSym;
+        }
+        const uint32_t qs = __shfl(qc, (int)ci);
+        uint32_t h = F + (qs != tw || qs >= q.sigma ? 1u : 0u);
+        h = up + 1 < h ? up + 1 : h;
+        F = finish(h, r);
+        if (hopeless(F)) return kVerifyInf << 6;
+    }
+    uint32_t key = (F << 6) | lane;
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        const uint32_t o = __shfl_xor(key, d);
+        key = o < key ? o : key;
+    }
+    return key;
+}
+
 }  // namespace fmx

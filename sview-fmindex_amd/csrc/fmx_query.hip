@@ -298,6 +298,47 @@ __global__ __launch_bounds__(256) void k_vote(const VoteBatch B) {
     }
 }
 
+// ---------------------------------------------------------------- k_verify
+// fmx_verify_async (include/fmx.h): a read against the text around each of its
+// candidate positions.  A wavefront per candidate slot, 4 slots per workgroup;
+// waves share nothing (no LDS, no barrier).  The forward pass (verify_pass,
+// fmx_kernels.hpp) gives the distance D and, with the smallest lane attaining
+// it, the earliest cheapest end; the backward pass is the same routine over the
+// reversed read and text from that end alone, and its smallest lane is the
+// largest start.  Candidates whose band misses the text altogether never start
+// a pass, which also keeps every j = r + P - band + k far inside 64 bits.
+__global__ __launch_bounds__(256) void k_verify(const VerifyBatch B) {
+    const uint32_t lane = threadIdx.x & 63, K = B.max_cands, band = B.band;
+    const uint64_t c = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (c >= B.nv * K) return;
+    const uint64_t v = c / K;
+    uint32_t dist = 0;
+    int64_t tstart = 0, tend = 0;
+    if (c - v * K < B.ncands[v]) {
+        dist = FMX_VERIFY_NONE;
+        const bool both = B.strands == FMX_BOTH_STRANDS, rc = both ? (v & 1) != 0 : B.strands != 0;
+        const uint64_t i = both ? v >> 1 : v, beg = B.offs[i], m = B.offs[i + 1] - beg;
+        const int64_t P = B.pos[c], n = (int64_t)B.n;
+        if (m <= FMX_VERIFY_MAX_LEN && P <= n + (int64_t)band && P >= -(int64_t)m - (int64_t)band) {
+            const VerifyRead q{B.bytes + beg, rc ? B.tab->enc_rc : B.tab->enc, m, (B.rev != 0) != rc, B.sigma};
+            const uint32_t f = verify_pass(q, B.text, B.n, false, P, band, 64, B.max_dist, lane);
+            if ((f >> 6) < kVerifyInf && (f >> 6) <= B.max_dist) {
+                // tend = m + P - band + k; seen from the text's end it sits on lane 2 band - k of row 0
+                const uint32_t g =
+                    verify_pass(q, B.text, B.n, true, n - (int64_t)m - P, band, 2 * band - (f & 63), B.max_dist, lane);
+                dist = f >> 6;
+                tend = (int64_t)m + P - (int64_t)band + (int64_t)(f & 63);
+                tstart = P + (int64_t)band - (int64_t)(g & 63);
+            }
+        }
+    }
+    if (lane == 0) {
+        B.out_dist[c] = dist;
+        B.out_tstart[c] = tstart;
+        B.out_tend[c] = tend;
+    }
+}
+
 // ------------------------------------------- grouped launches: debug check
 // FMX_GROUP_CHECK=1 (fmx_index::group_check): after the place (and refine)
 // pass and before the search, the launch's sorted order is checked against
@@ -976,6 +1017,17 @@ hipError_t launch_vote(const fmx_index *ix, const VoteBatch &vb, hipStream_t str
     return hipGetLastError();
 }
 
+// The banded alignment of every candidate slot: k_verify, 4 slots per workgroup.
+hipError_t launch_verify(const fmx_index *, const VerifyBatch &vb, hipStream_t stream) {
+    if (vb.nv == 0) return hipSuccess;
+    if (vb.max_cands == 0 || vb.max_cands > kVoteMaxCands || vb.band > FMX_VERIFY_MAX_BAND || !vb.text ||
+        vb.nv > 4 * 0x7FFFFFFFull / vb.max_cands)
+        return hipErrorInvalidValue;
+    const uint64_t wgs = (vb.nv * vb.max_cands + 3) / 4;
+    hipLaunchKernelGGL(k_verify, dim3((uint32_t)wgs), dim3(256), 0, stream, vb);
+    return hipGetLastError();
+}
+
 static hipError_t check_group(const LocateGroup &grp, uint64_t *tiles) {
     if (grp.n == 0 || grp.n > kMaxGroup || grp.tile_begin[0] != 0) return hipErrorInvalidValue;
     uint64_t t = 0;
@@ -1065,7 +1117,7 @@ hipError_t build_dlut_rows(fmx_index *ix, hipStream_t stream) {
     return e;
 }
 
-hipError_t build_full_sa(fmx_index *ix, uint32_t stride, hipStream_t stream) {
+hipError_t build_full_sa(fmx_index *ix, uint32_t stride, hipStream_t stream, bool from_blob) {
     const uint64_t n = ix->bv.n;
     // padded: scan_rows reads whole 16-B vectors of row records
     ix->safull_bytes = std::max<uint64_t>(n, 1) * ix->bv.L.pos_bytes * stride + 64;
@@ -1075,7 +1127,12 @@ hipError_t build_full_sa(fmx_index *ix, uint32_t stride, hipStream_t stream) {
     if (e != hipSuccess) return e;
     {
         const Disp d = dispatch(ix);
-        e = d.ops->full_sa(ix->qa, d.vb, d.rec, n, ix->d_safull, stride, stream);
+        QueryArgs qa = ix->qa;
+        if (from_blob) {  // (the faithful index's multi-line records have no row walk of their own)
+            qa.occ = nullptr;
+            qa.rec_bytes = 0;
+        }
+        e = d.ops->full_sa(qa, d.vb, from_blob ? 0u : d.rec, n, ix->d_safull, stride, stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
     return e;
