@@ -90,7 +90,7 @@ __global__ __launch_bounds__(256) void k_encode(const uint8_t *__restrict__ text
 // (idx+1) of t[i..i+k), 0 past the end, most significant first.
 __global__ __launch_bounds__(256) void k_kmer_hist(const uint8_t *__restrict__ t, uint64_t n, uint32_t k, uint64_t W,
                                                    uint64_t bins, unsigned long long *__restrict__ hist) {
-    extern __shared__ uint32_t lh[];
+    FMX_DYN_LDS_AS(uint32_t, lh);
     const bool use_lds = bins <= 8192;
     if (use_lds) {
         for (uint64_t b = threadIdx.x; b < bins; b += 256) lh[b] = 0;
@@ -431,7 +431,7 @@ static fmx_status suffix_array(const uint8_t *t, uint64_t n1, uint32_t alphabet,
 
 __global__ __launch_bounds__(256) void k_bucket_of(const uint8_t *__restrict__ t, uint64_t n1, uint32_t W,
                                                    uint32_t *__restrict__ hist) {
-    extern __shared__ uint32_t lh[];
+    FMX_DYN_LDS_AS(uint32_t, lh);
     for (uint32_t b = threadIdx.x; b < W * W; b += 256) lh[b] = 0;
     __syncthreads();
     for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n1; i += (uint64_t)gridDim.x * 256) {
@@ -446,7 +446,7 @@ __global__ __launch_bounds__(256) void k_bucket_of(const uint8_t *__restrict__ t
 // of workgroup g's positions in bucket b (exclusive scan over (b, g))
 __global__ __launch_bounds__(256) void k_bucket_scatter(const uint8_t *__restrict__ t, uint64_t n1, uint32_t W,
                                                         const uint64_t *__restrict__ base, uint64_t *__restrict__ sa) {
-    extern __shared__ unsigned long long cur[];
+    FMX_DYN_LDS_AS(unsigned long long, cur);
     for (uint32_t b = threadIdx.x; b < W * W; b += 256) cur[b] = base[(uint64_t)blockIdx.x * W * W + b];
     __syncthreads();
     for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n1; i += (uint64_t)gridDim.x * 256) {

@@ -24,6 +24,9 @@
 #ifndef FMX_DYN_LDS
 #define FMX_DYN_LDS(name) extern __shared__ uint8_t name[]
 #endif
+#ifndef FMX_DYN_LDS_AS  // ... as an array of T (the builder's histograms)
+#define FMX_DYN_LDS_AS(T, name) extern __shared__ T name[]
+#endif
 
 namespace fmx {
 

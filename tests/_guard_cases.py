@@ -99,13 +99,16 @@ class Arena:
         self.mem_cls = mem_cls
         self.cur = 0
         self.bufs = {}   # name -> (offset, nbytes)
-        self.init = {}   # name -> initial bytes (an input) or None (an output: 0x5A)
+        self.init = {}   # name -> initial bytes (an input) or None (an output: 0x5A, or the guard's 0xA5)
+        self.fill = {}   # name -> what an output holds before the call (FILL_OUT unless carved otherwise)
         self.mem = None
 
-    def carve(self, name, nbytes, align, skew, boundary=16, data=None, tail=0):
+    def carve(self, name, nbytes, align, skew, boundary=16, data=None, tail=0, fill=FILL_OUT):
         """A buffer of exactly nbytes at (a `boundary`-byte boundary) + skew,
         GUARD bytes or more after the previous one, and `tail` more guard
-        bytes after it than the next carve's GUARD."""
+        bytes after it than the next carve's GUARD.  fill: what an output
+        (data None) holds before the call — FILL_GUARD makes it look like the
+        guards around it (a blob area that must not be assumed zero)."""
         assert skew % align == 0 and skew < boundary and name not in self.bufs
         off = -(-(self.cur + GUARD) // boundary) * boundary + skew
         if data is not None:
@@ -113,6 +116,7 @@ class Arena:
             assert data.size == nbytes
         self.bufs[name] = (off, nbytes)
         self.init[name] = data
+        self.fill[name] = fill
         self.cur = off + nbytes + tail
         return name
 
@@ -121,7 +125,7 @@ class Arena:
         host = np.full(self.size, FILL_GUARD, np.uint8)
         self.is_guard = np.ones(self.size, bool)
         for name, (off, nb) in self.bufs.items():
-            host[off:off + nb] = FILL_OUT if self.init[name] is None else self.init[name]
+            host[off:off + nb] = self.fill[name] if self.init[name] is None else self.init[name]
             self.is_guard[off:off + nb] = False
         self.mem = self.mem_cls(self.size)
         assert self.mem.base % 256 == 0

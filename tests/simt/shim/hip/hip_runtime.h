@@ -1,7 +1,9 @@
 // TEST INFRASTRUCTURE — a host-only stand-in for <hip/hip_runtime.h> under
 // which the engine's own sources (sview-fmindex_amd/csrc: fmx_api.cpp,
-// fmx_query.hip, fmx_layout.hip, fmx_kernels.hpp, fmx_device.hpp) compile as
-// plain C++ and run on the CPU (tests/simt/libfmx_simt.so).  Kernels run as
+// fmx_query.hip, fmx_layout.hip, fmx_build.hip, fmx_kernels.hpp,
+// fmx_device.hpp) compile as plain C++ and run on the CPU
+// (tests/simt/libfmx_simt.so; the builder's rocPRIM calls go to
+// shim/rocprim/rocprim.hpp).  Kernels run as
 // one fiber per work-item (tests/simt/simt_rt.cpp): workgroups in a shuffled
 // order, the work-items of a workgroup interleaved at random between
 // barriers, wave operations (__shfl*, __all, readfirstlane) exchanged per
@@ -33,6 +35,7 @@
 // section that simt_rt fills with random bytes before every workgroup
 #define __shared__ static __attribute__((section("simt_lds")))
 #define FMX_DYN_LDS(name) uint8_t *name = ::simt::dyn_lds()
+#define FMX_DYN_LDS_AS(T, name) T *name = reinterpret_cast<T *>(::simt::dyn_lds())
 
 struct dim3 {
     uint32_t x, y, z;
@@ -134,6 +137,11 @@ void land_before_launch(hipStream_t s);
 // then a failure is reported by the next synchronisation of s, as on the GPU.
 hipError_t submit_launch(hipStream_t s, std::function<hipError_t()> launch);
 
+// The emulator's seeded random stream (simt_config), for host-side stand-ins
+// of device libraries (shim/rocprim/rocprim.hpp): one draw, and n random bytes at p.
+uint64_t host_random();
+void host_fill_random(void *p, size_t n);
+
 template <class... KP, class... A>
 hipError_t launch_kernel(void (*k)(KP...), dim3 g, dim3 b, size_t lds, hipStream_t s, A &&...a) {
     static_assert(sizeof...(KP) == sizeof...(A), "kernel argument count");
@@ -174,6 +182,7 @@ inline unsigned long long atomicAdd(unsigned long long *p, unsigned long long v)
 inline uint64_t atomicAdd(uint64_t *p, uint64_t v) { return ::simt::atomic_add(p, v); }
 inline int atomicAdd(int *p, int v) { return ::simt::atomic_add(p, v); }
 inline uint32_t atomicOr(uint32_t *p, uint32_t v) { return ::simt::atomic_or(p, v); }
+inline int __popcll(unsigned long long x) { return __builtin_popcountll(x); }
 
 // k_locate's hand-off (fmx_kernels.hpp, FMX_HANDOFF): plain accesses, each a
 // possible switch point; the wall clock in 10 ns ticks.  Workgroups run one at

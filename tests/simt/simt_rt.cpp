@@ -316,6 +316,17 @@ void maybe_yield() {
 
 void set_last_error(hipError_t e) { g_last = e; }
 
+uint64_t host_random() {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    init_once();
+    return rnd();
+}
+void host_fill_random(void *p, size_t n) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    init_once();
+    fill_random(p, n, g_rng);
+}
+
 hipError_t run_grid(dim3 grid, dim3 block, size_t dyn_bytes, const std::function<void()> &body) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     init_once();
@@ -499,7 +510,9 @@ std::recursive_mutex g_q_mu;
 bool g_defer = false;
 double g_progress = 0.25;  // chance that a host API call runs some queued work
 std::mt19937_64 g_q_rng(0xdefe);
-std::vector<simt_stream *> g_streams;  // (never freed: events may outlive their stream)
+// (never freed: events may outlive their stream; the list itself outlives static destruction, so a
+// leak check at exit sees the records as reachable)
+std::vector<simt_stream *> &g_streams = *new std::vector<simt_stream *>;
 int g_q_depth = 0;
 
 void drain(simt_stream *s, uint64_t upto) {

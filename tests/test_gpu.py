@@ -8,6 +8,8 @@ import os
 import numpy as np
 import pytest
 
+from _build_cases import check_parity, every_layout_inputs  # (shared with the emulator's builder tests)
+from _build_cases import engine_build as gpu_build
 from _util import (ALL_LAYOUTS, encode, occurrences, rand_chr_list, rand_pattern, rand_text,
                    table_from_symbols)
 
@@ -29,129 +31,6 @@ def block_of(pkg, planes, vb):
 
 def pos_of(pkg, pb):
     return pkg.u32 if pb == 4 else pkg.u64
-
-
-def gpu_build(pkg, text, sigma, pb, planes, vb, k, sr, table):
-    enc = pkg.text_encoders.EncodingTable(table) if table is not None else pkg.text_encoders.PassThrough()
-    LT = pkg.build_config.LookupTableConfig.KmerSize(k) if k > 1 else pkg.build_config.LookupTableConfig.None_()
-    SA = pkg.build_config.SuffixArrayConfig.Compressed(sr) if sr > 1 else pkg.build_config.SuffixArrayConfig.Uncompressed()
-    b = (pkg.FmIndexBuilder(len(text), sigma, enc, pos_of(pkg, pb), block_of(pkg, planes, vb))
-         .set_lookup_table_config(LT).set_suffix_array_config(SA))
-    blob = pkg.aligned_buffer(b.blob_size())
-    b.build(np.frombuffer(bytes(text), np.uint8), blob)
-    return blob
-
-
-def diagnose(pkg, ix, load, data, offsets, pats, goff, ooff):
-    """On a count mismatch, what the failure looks like (kept in the assert
-    message): the patterns that differ, whose count they got, the count path's
-    answer for them, whether the same call differs again (three reruns on this
-    index) and the answer of a fresh index in launch order (FMX_GROUPED=0)."""
-    oc = np.diff(ooff.astype(np.int64))
-    bad = np.flatnonzero(np.diff(goff.astype(np.int64)) != oc)
-    gc = np.diff(goff.astype(np.int64))
-    out = [f"{bad.size} of {len(pats)} patterns differ"]
-    for b in bad[:6]:
-        same = sorted({pats[j] for j in np.flatnonzero(oc == gc[b])})[:3]
-        out.append(f"pat {b} {pats[b]!r}: gpu {gc[b]} oracle {oc[b]} (the oracle count of {same!r})")
-    try:
-        d2, o2 = pkg.pack_patterns(pats)
-        if not (np.array_equal(d2, data) and np.array_equal(o2, offsets)):
-            diff = np.flatnonzero(d2 != data)
-            out.append(f"the caller's pattern buffer changed since packing at bytes {diff[:8].tolist()}")
-        c2 = ix.count_batch((d2.copy(), o2.copy())).astype(np.int64)
-        out.append(f"count path on a fresh copy: {np.flatnonzero(c2 != oc).size} differ")
-        cnt = ix.count_batch((data, offsets)).astype(np.int64)
-        out.append(f"count path on those: {cnt[bad[:6]].tolist()}")
-        for r in range(3):
-            g2, _ = ix.locate_batch((data, offsets))
-            b2 = np.flatnonzero(np.diff(g2.astype(np.int64)) != oc)
-            out.append(f"rerun {r}: {b2.size} differ {b2[:6].tolist()}")
-        saved = os.environ.get("FMX_GROUPED")
-        os.environ["FMX_GROUPED"] = "0"
-        try:
-            ix2 = load()
-            g3, _ = ix2.locate_batch((data, offsets))
-            ix2.close()
-        finally:
-            if saved is None:
-                os.environ.pop("FMX_GROUPED", None)
-            else:
-                os.environ["FMX_GROUPED"] = saved
-        b3 = np.flatnonzero(np.diff(g3.astype(np.int64)) != oc)
-        out.append(f"fresh index, launch order: {b3.size} differ {b3[:6].tolist()}")
-    except Exception as e:  # (the diagnosis must not hide the original failure)
-        out.append(f"diagnosis stopped: {e!r}")
-    return "; ".join(out)
-
-
-class BufferWatch:
-    """Copies of the caller's buffers (patterns, offsets, blob) taken before
-    the oracle reads them, compared after the oracle call and after every GPU
-    call: a recurrence of the round-4 failure (the GPU answered
-    as if a few pattern bytes differed from the caller's buffer) classifies
-    itself — the message names the first call after which a buffer differed
-    from its copy, and where, or says that every buffer was intact."""
-
-    def __init__(self, **bufs):
-        self.bufs = bufs
-        self.copies = {k: np.array(v, copy=True) for k, v in bufs.items()}
-        self.first_change = None
-
-    def check(self, after):
-        if self.first_change:
-            return
-        for k, v in self.bufs.items():
-            if not np.array_equal(v, self.copies[k]):
-                at = np.flatnonzero(np.asarray(v).view(np.uint8) != self.copies[k].view(np.uint8))
-                self.first_change = f"{k} changed after {after} at bytes {at[:8].tolist()}"
-                return
-
-    def report(self):
-        return self.first_change or "caller's buffers intact after every call"
-
-
-def check_parity(pkg, O, blob, pb, planes, vb, enc, pats, occ, reversed_too=True, expect_path=None):
-    """Counts and locations of `pats` on the GPU against the oracle, forward
-    (and reversed).  expect_path: "grouped" / "grouped_raw" / "ordered" —
-    the launch path the first locate must have taken (fmx_index_info's
-    launch counters)."""
-    L = O.layout(pb, planes, vb, enc)
-    data, offsets = pkg.pack_patterns(pats)
-    watch = BufferWatch(data=data, offsets=offsets, blob=blob)
-    orc = O.OracleIndex(blob, L)
-    encoder = pkg.text_encoders.EncodingTable if enc == 0 else pkg.text_encoders.PassThrough
-
-    def load():
-        return pkg.FmIndex.load(blob, pos_of(pkg, pb), block_of(pkg, planes, vb), encoder, options=occ)
-    ooff, olocs = orc.locate_batch(data, offsets)
-    watch.check("the oracle")
-    ix = load()
-    watch.check("FmIndex.load")
-    goff, glocs = ix.locate_batch((data, offsets))
-    watch.check("locate_batch")
-    if expect_path is not None:
-        info = ix.info()
-        took = {k: info["launches_" + k] for k in ("grouped", "grouped_raw", "ordered")}
-        assert took[expect_path] >= 1 and sum(took.values()) == took[expect_path], \
-            f"the locate did not run {expect_path} alone: {took}"
-    if not np.array_equal(goff, ooff):
-        pytest.fail("per-pattern counts / offsets differ: " + diagnose(pkg, ix, load, data, offsets, pats, goff,
-                                                                        ooff) + "; " + watch.report())
-    assert np.array_equal(glocs, olocs), "locations differ (SA-row order); " + watch.report()
-    cnt = ix.count_batch((data, offsets))
-    watch.check("count_batch")
-    assert np.array_equal(cnt.astype(np.uint64), np.diff(ooff)), "count path differs; " + watch.report()
-    if reversed_too:
-        rpats = [p[::-1] for p in pats]
-        rc = ix.count_batch(rpats, reversed=True)
-        assert np.array_equal(rc, cnt)
-        roff, rlocs = ix.locate_batch(rpats, reversed=True)
-        assert np.array_equal(roff, ooff) and np.array_equal(rlocs, olocs)
-    ix.close()
-    watch.check("close")
-    assert watch.first_change is None, watch.report()
-    return ooff, olocs
 
 
 def test_readme_known_answers_gpu(pkg, O):
@@ -196,21 +75,10 @@ def test_golden_blobs_on_gpu(pkg, O):
 def test_builder_and_queries_every_layout(pkg, O, pb, planes, vb):
     """get_accurate_result-style sweep on the GPU: builder bytes, then count and
     locate against the oracle for both device occ layouts."""
-    rng = np.random.default_rng(pb * 1000 + planes * 100 + vb)
-    for sigma in sorted({2, 3, (1 << planes) // 2 + 1, 1 << planes}):
-        chars = rand_chr_list(rng, sigma)
-        table = table_from_symbols([bytes([c]) for c in chars])
-        text = rand_text(rng, chars, 300, 2000)
-        k, sr = int(rng.integers(1, 5)), int(rng.integers(1, 5))
-        if (sigma + 1) ** k > 1 << 20:
-            k = 2
+    for sigma, chars, table, text, k, sr, pats in every_layout_inputs(pb, planes, vb):
         blob = gpu_build(pkg, text, sigma, pb, planes, vb, k, sr, table)
         ref = O.build(text, sigma, O.layout(pb, planes, vb), k, sr, table)
         assert np.array_equal(blob, ref), f"builder differs sigma={sigma} k={k} sr={sr}"
-        pats = [rand_pattern(rng, text, 1, 24) for _ in range(300)]
-        pats += [bytes(rng.choice(np.frombuffer(chars, np.uint8), size=int(rng.integers(1, 12))))
-                 for _ in range(50)]                              # mostly absent
-        pats += [b"\x00", b"\x7f\x7f", chars[:1] * 2]              # wildcard bytes, short repeats
         for occ in OCC_MODES:
             check_parity(pkg, O, blob, pb, planes, vb, 0, pats, occ)
 
